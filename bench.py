@@ -38,6 +38,12 @@ resident, and one step = one whole job = `dist.exchange_counts` (collective 1)
 the timed region.  With N > 1 ranks the default line carries both modes as
 side records (`configs_3_corpus_sharded`, `configs_4_longform_sharded`).
 `--gpus N` without a torchrun environment starts the N workers itself.
+
+`--dump-outputs DIR` writes what the last timed step computed - the per-word
+scores a caller receives, in input order, with the words per utterance to
+split them - as DIR/<name>.npy (float32 / float64; `_rank<r>` suffixed per
+rank of an N > 1 batch run).  The inputs are seeded, so two builds given the
+same arguments can be compared output for output.
 """
 import argparse
 import csv
@@ -131,6 +137,10 @@ def parse_args():
                              'next to this script (bench_side_<workload / '
                              'config / precision>.json for the non-default '
                              'commands)')
+    parser.add_argument('--dump-outputs', default=None, metavar='DIR',
+                        help='after the timed steps, write what the last '
+                             'timed step computed as DIR/<name>.npy '
+                             '(float32 / float64, at most 64 MB in all)')
     parser.add_argument('--cpu-worker', type=float, default=None,
                         help=argparse.SUPPRESS)
     return parser.parse_args()
@@ -539,6 +549,31 @@ def timed_regions(runner, steps, warmup, regions, world, exchange=None,
             elapsed = float(slowest.item())
         laps.append(elapsed)
     return laps, ramp, scores
+
+
+DUMP_LIMIT = 64 * 2 ** 20 - 2 ** 16    # bytes of array data (room for headers)
+
+
+def dump_outputs(directory, arrays):
+    """`arrays` (name -> tensor or array) as `directory/<name>.npy`: float64
+    and integers as float64, everything else as float32.  Over `DUMP_LIMIT` in
+    all, each array is cut to the same fixed, seeded sample of its elements
+    (flattened, in order)."""
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, value in arrays.items():
+        value = value.detach().cpu().numpy() if torch.is_tensor(value) else \
+            np.asarray(value)
+        wide = value.dtype == np.float64 or value.dtype.kind in 'iub'
+        host[name] = value.astype(np.float64 if wide else np.float32)
+    total = sum(value.nbytes for value in host.values())
+    for name, value in host.items():
+        if total > DUMP_LIMIT:
+            keep = value.size * DUMP_LIMIT // total
+            index = np.sort(np.random.default_rng(0).choice(
+                value.size, keep, replace=False))
+            value = value.reshape(-1)[index]
+        np.save(os.path.join(directory, f'{name}.npy'), value)
 
 
 def profile_file(name):
@@ -1458,7 +1493,9 @@ def sharded_job(workload, args, rank, world, device, steps, warmup, regions,
         laps.append(float(slowest.item()))
     # every rank holds every score: the checksums must agree across ranks
     # (summed on the host: one order whatever device the scores came back on)
-    checksum = flat.cpu().double().sum().reshape(1).to(wire)
+    host_flat = flat.cpu()
+    outputs = {'scores': host_flat, 'words_per_utterance': sizes.cpu()}
+    checksum = host_flat.double().sum().reshape(1).to(wire)
     lowest, highest = checksum.clone(), checksum.clone()
     torch.distributed.all_reduce(lowest, op=torch.distributed.ReduceOp.MIN)
     torch.distributed.all_reduce(highest, op=torch.distributed.ReduceOp.MAX)
@@ -1505,7 +1542,7 @@ def sharded_job(workload, args, rank, world, device, steps, warmup, regions,
     line['hbm_frac_compulsory'] /= world
     del runner
     torch.cuda.empty_cache()
-    return line, kernels, passes
+    return line, kernels, passes, outputs
 
 
 def free_port():
@@ -1785,11 +1822,14 @@ def main():
 def run_sharded(args, rank, world, device, host):
     """`--workload corpus | longform`: one line for the whole strong-scaled
     job."""
-    line, kernels, passes = sharded_job(
+    line, kernels, passes, outputs = sharded_job(
         args.workload, args, rank, world, device, args.steps, args.warmup,
         args.regions)
     if rank != 0:
         return
+    if args.dump_outputs:
+        # (every rank holds the whole job's scores; rank 0 writes them)
+        dump_outputs(args.dump_outputs, outputs)
     roof, committed = roofline(
         kernels, passes, None, 'conv', spans=kernels.pop('_stack_spans', None),
         layers=1 + cfg.DEFAULT.layers)
@@ -1862,6 +1902,14 @@ def run_batch(args, rank, world, device, host):
     laps, ramp, scores = timed_regions(
         runner, args.steps, args.warmup, args.regions, world, exchange,
         skip_preroll=args.no_preroll)
+    if args.dump_outputs:
+        # the last timed step's scores as the API hands them back (per word,
+        # input order; timed_regions has synchronised the device)
+        suffix = f'_rank{rank}' if world > 1 else ''
+        dump_outputs(args.dump_outputs, {
+            f'scores{suffix}': scores[columns],
+            f'words_per_utterance{suffix}': np.bincount(
+                plan.utterance, weights=plan.words, minlength=len(audios))})
     if world > 1:
         # every rank now holds every rank's scores: its own rows came back intact
         mine = gathered_all.view(world, rows, most_words)[rank]

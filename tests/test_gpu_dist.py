@@ -197,6 +197,46 @@ def test_bench_refuses_a_mismatched_world():
 
 
 @pytest.mark.timeout(900)
+def test_bench_dump_outputs_are_the_api_scores(tmp_path):
+    """`bench.py --dump-outputs DIR` on one GPU: the last timed step's
+    per-word scores are what `from_alignments_and_audios` returns for the same
+    seeded utterances, split by the dumped word counts, and a second run
+    writes the same arrays bit for bit."""
+    import json
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f'run{run}'
+        child = subprocess.run(
+            [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1',
+             '--steps', '3', '--warmup', '1', '--regions', '1',
+             '--no-preroll', '--no-cpu-baseline', '--no-api', '--no-side',
+             '--side-records', str(tmp_path / 'side.json'),
+             '--dump-outputs', str(out)],
+            cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert child.returncode == 0, child.stderr[-3000:]
+        line = json.loads(child.stdout.strip().splitlines()[-1])
+        assert line['steps'] == 3 and line['ms_per_step'] > 0
+        dumps.append({name: np.load(out / f'{name}.npy')
+                      for name in ('scores', 'words_per_utterance')})
+    first, second = dumps
+    for name in first:
+        assert np.array_equal(first[name], second[name]), name
+    assert first['scores'].dtype == np.float32
+    assert first['words_per_utterance'].dtype == np.float64
+    sys.path.insert(0, ROOT)
+    import bench
+    audios, alignments, bounds = bench.workload(0)
+    counts = [b.shape[1] for b in bounds]
+    assert first['words_per_utterance'].tolist() == counts
+    assert first['scores'].shape == (sum(counts),)
+    want = emphases_amd.from_alignments_and_audios(
+        alignments, [torch.from_numpy(a) for a in audios], gpu=0)
+    want = torch.cat([w.reshape(-1).cpu() for w in want]).numpy()
+    assert np.abs(first['scores'] - want).max() < 1e-5
+
+
+@pytest.mark.timeout(900)
 def test_sharded_file_api(tmp_path):
     """dist.from_files_to_files (core.py:115-179 over a process group): 200
     WAV + TextGrid files (some at 8 and 22.05 kHz), two gloo ranks sharing the

@@ -1597,3 +1597,39 @@ def test_bench_line_stays_under_the_driver_limit(tmp_path, monkeypatch):
     monkeypatch.setattr(sys, 'argv', ['bench.py'])
     assert bench.side_path(bench.parse_args()) == \
         os.path.join(ROOT, 'bench_side.json')
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: one .npy per array, float32 or float64
+    (integers exactly, as float64); over the size limit every array keeps the
+    same seeded sample of its elements, in order, and two dumps agree."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--dump-outputs', 'out'])
+    assert bench.parse_args().dump_outputs == 'out'
+    scores = torch.linspace(0., 1., 1000)
+    counts = np.array([600, 400], dtype=np.int64)
+    bench.dump_outputs(tmp_path / 'small', {
+        'scores': scores, 'words_per_utterance': counts,
+        'wide': np.arange(3, dtype=np.float64), 'half': scores.half()})
+    got = {name: np.load(tmp_path / 'small' / f'{name}.npy')
+           for name in ('scores', 'words_per_utterance', 'wide', 'half')}
+    assert got['scores'].dtype == np.float32 and \
+        np.array_equal(got['scores'], scores.numpy())
+    assert got['words_per_utterance'].dtype == np.float64 and \
+        np.array_equal(got['words_per_utterance'], counts)
+    assert got['wide'].dtype == np.float64 and got['half'].dtype == np.float32
+    # 8 KB of data against a 2 KB limit: a quarter of each array
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 2048)
+    big = {'a': np.arange(1024, dtype=np.float32),
+           'b': np.arange(1024, dtype=np.float32)}
+    for name in ('first', 'second'):
+        bench.dump_outputs(tmp_path / name, big)
+    sizes = 0
+    for key in big:
+        first = np.load(tmp_path / 'first' / f'{key}.npy')
+        assert np.array_equal(first, np.load(tmp_path / 'second' / f'{key}.npy'))
+        assert first.size == 256 and np.all(np.diff(first) > 0)
+        sizes += first.nbytes
+    assert sizes <= 2048
