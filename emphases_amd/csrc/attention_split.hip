@@ -13,8 +13,10 @@
 //     PIECES = 2 ("bf16x3"):  a.b ~ a0.b0 + a0.b1 + a1.b0            3 MFMAs,
 //         pieces rounded to nearest: each product within 2^-16 of exact
 //     PIECES = 3 ("bf16x6"):  + a0.b2 + a1.b1 + a2.b0                6 MFMAs,
-//         pieces by truncation, x0 + x1 + x2 == x EXACTLY; the three dropped
-//         products are below 2^-23 of the result: the error of one fp32 rounding
+//         pieces rounded to nearest, x0 + x1 + x2 == x EXACTLY; the three dropped
+//         products are below 2^-26 of |a.b| and of either sign (truncated pieces
+//         left a same-signed 2^-20 that added up over the keys: 4x the error of
+//         bf16x3 on the scores, tests/test_gpu_paths.py)
 // against 16 units of pipe time for the fp32 instruction.
 //
 // Shapes.  S^T = K Q^T (keys are MFMA rows, queries columns) in 32 x 32 tiles, the

@@ -500,7 +500,8 @@ using namespace emph;
 
 namespace {
 
-// the pieces of split_pair (split.h) on the host: two, rounded to nearest; three, truncated
+// the weights' pieces on the host: two rounded to nearest, as split_pair (split.h); three
+// truncated - exact, like split_pair's three rounded ones
 void p16_host_pieces(float value, int pieces, uint16_t (&out)[3]) {
     for (int piece = 0; piece < pieces; ++piece) {
         uint32_t bits;

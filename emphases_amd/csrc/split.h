@@ -29,15 +29,21 @@ __device__ __forceinline__ void split_pair(float a, float b, uint32_t (&out)[PIE
         out[0] = bits;
         out[1] = __builtin_bit_cast(uint32_t, low);
     } else {
-        // truncation, three times: exact (8 + 8 + 8 bits)
+        // round to nearest, three times: x0 + x1 + x2 == x EXACTLY (each remainder is
+        // exact in fp32; the third holds at most 8 significant bits).  Rounded, not
+        // truncated: truncated pieces all carry the sign of x, so the dropped products
+        // (x1 y2, x2 y1, x2 y2: 2^-20 of |x y| truncated, 2^-26 rounded) were a BIAS
+        // that added up over the keys of the softmax instead of averaging out
         float ra = a, rb = b;
 #pragma unroll
         for (int piece = 0; piece < PIECES; ++piece) {
-            const uint32_t ua = __float_as_uint(ra), ub = __float_as_uint(rb);
-            out[piece] = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
+            const bf16x2 part = {static_cast<__bf16>(ra), static_cast<__bf16>(rb)};
+            uint32_t bits = __builtin_bit_cast(uint32_t, part);
+            asm("" : "+v"(bits));         // (as above: one real conversion per pair)
+            out[piece] = bits;
             if (piece + 1 < PIECES) {
-                ra -= __uint_as_float(ua & 0xffff0000u);
-                rb -= __uint_as_float(ub & 0xffff0000u);
+                ra -= __uint_as_float(bits << 16);
+                rb -= __uint_as_float(bits & 0xffff0000u);
             }
         }
     }

@@ -60,6 +60,52 @@ SHORT, LONG = (0, GROUPED_FROM - 1), (GROUPED_FROM, EVERYTHING)
 FEW_WORDS, MANY_WORDS = (0, FUSED_WORDS), (FUSED_WORDS + 1, EVERYTHING)
 WORD_TILE = 16
 WINOGRAD_LDS_BUDGET = 160 * 1024
+# the packed frame axis a launch may address: the 16-position split kernels
+# take ld < 2^22 (csrc/block_split16.hip), the 32-position ones and the fp32
+# projection / block / conv kernels less than 2^28 or 2^29.  A plan at or past
+# the limit of its engine runs as consecutive sub-plans below it (`forward`)
+SPLIT16_COLUMNS = 1 << 22
+KERNEL_COLUMNS = 1 << 28
+HEAD_DIMS = (32, 40, 64)
+
+
+def check_supported(config):
+    """Raise ValueError for a configuration the kernels cannot run, before
+    anything is allocated or launched: the limits the EMPH_REQUIRE checks of
+    the kernels a configuration selects impose."""
+    channels = config.channels
+    if channels > 128:
+        # emph_segment_reduce, emph_add_layernorm, emph_word_decoder
+        raise ValueError(f'channels {channels} > 128: the word reduce and '
+                         'the LayerNorm hold at most 128 channels')
+    if config.architecture == 'transformer':
+        head_dim = channels // config.heads
+        if head_dim not in HEAD_DIMS:
+            # emph_attention, emph_attention_split
+            raise ValueError(
+                f'head dimension {head_dim} (channels {channels} / heads '
+                f'{config.heads}) not in {{32, 40, 64}}')
+    elif config.layers > 16:
+        # emph_prominence_forward, emph_word_decoder
+        raise ValueError(f'{config.layers} convolution layers > 16')
+    if config.architecture == 'convolution' or not config.has_decoder:
+        # the fused word stage (emph_word_decoder)
+        if channels < 16 or channels % 16:
+            raise ValueError(
+                f'channels {channels} not a multiple of 16 in 16..128 (the '
+                'fused word stage of this configuration)')
+        if config.decoder_kernel_size not in (1, 3, 5):
+            raise ValueError(
+                f'decoder kernel size {config.decoder_kernel_size} not in '
+                '{1, 3, 5} (the fused word stage of this configuration)')
+        layers = config.layers if config.has_decoder else 0
+        if runtime.library().emph_word_decoder_block(
+                layers, config.decoder_kernel_size,
+                config.decoder_kernel_size) < 16:
+            raise ValueError(
+                f'{layers} decoder layers of kernel size '
+                f'{config.decoder_kernel_size}: the receptive field is too '
+                "wide for the fused word stage's 64-word window")
 
 
 def a_weighting():
@@ -124,6 +170,7 @@ class Engine:
         if precision not in PRECISIONS:
             raise ValueError(
                 f'precision {precision!r} is not one of {sorted(PRECISIONS)}')
+        check_supported(config)
         self.config = config
         self.precision = precision
         self.split_pieces, self.attention_pieces, self.linear_pieces = \
@@ -149,6 +196,10 @@ class Engine:
         self.split_tile = int(os.environ.get('EMPHASES_SPLIT_TILE', 16))
         if self.split_tile not in (16, 32):
             raise ValueError('EMPHASES_SPLIT_TILE must be 16 or 32')
+        # the packed frame axis of one pass stays below this (see `sub_plans`)
+        self.max_columns = SPLIT16_COLUMNS if (
+            config.architecture == 'transformer' and self.linear_pieces and
+            self.split_tile == 16) else KERNEL_COLUMNS
         state = weights_module.load(state, config)
         self.state = state
         dev = self.device
@@ -362,8 +413,11 @@ class Engine:
                         in_w[part * channels:(part + 1) * channels], True)
                     for part in range(3)])), to(in_b.astype(np.float32)))
             # precision='bf16x3': the same two launches on the bf16 matrix pipe
+            # (80 channels in two heads: the projections write the split
+            # attention's per-head images)
             block_split = qkv_split = None
-            if self.linear_pieces and channels == 80 and block is not None:
+            if self.linear_pieces and channels == 80 and config.heads == 2 and \
+                    block is not None:
                 pieces = self.linear_pieces
                 pack = functools.partial(
                     runtime.linear_split_pack, pieces=pieces,
@@ -833,11 +887,9 @@ class Engine:
                     counts_pointer, runtime.stream()), 'emph_attention')
 
         split_tiles, wide = None, self.split_tile
-        # (the 16-position kernels address rows with 32-bit byte offsets: a packed
-        # axis of 2^22 columns or more - 11 hours of frames in ONE batch - takes the
-        # fp32 position-wise kernels)
-        if axis == runtime.AXIS_FRAMES and ld < (1 << 22 if wide == 16 else 1 << 29) \
-                and ('tiles', axis, wide) + select in meta:
+        # (the 16-position kernels address rows with 32-bit byte offsets: `forward`
+        # keeps every packed axis below 2^22 columns for them, `sub_plans`)
+        if axis == runtime.AXIS_FRAMES and ('tiles', axis, wide) + select in meta:
             split_tiles = meta[('tiles', axis, wide) + select]
 
         def position_wise(layer, following):
@@ -1140,6 +1192,14 @@ class Engine:
         undefined).  The tensors are workspace buffers: they are overwritten
         by the next forward() of this engine."""
         config = self.config
+        runs = self.sub_plans(plan)
+        if runs is not None:
+            if stages is not None:
+                # (the stage dump is a test tap of one packed layout)
+                raise ValueError(
+                    'stages of a plan past the packed-axis limit: pass its '
+                    'segments in smaller plans')
+            return self._forward_runs(audio, plan, runs, tracks, features)
         meta = meta or self.upload(plan)
         block = meta['tile']
         channels = config.channels
@@ -1261,6 +1321,88 @@ class Engine:
             stages['downsampled'] = wa.clone()
         return self._word_stage(wa, plan, meta, logits, scores)
 
+    def sub_plans(self, plan):
+        """None when one pass takes the whole plan; else the (first, end)
+        segment ranges of consecutive sub-plans whose packed frame axes - and
+        word-piece axes for DOWNSAMPLE_LOCATION='input' - each stay below
+        `max_columns`.  Segments are independent, so the scores are bitwise
+        those of one pass, with the same kernels at every size."""
+        from . import batch
+        pieces = self.config.downsample_location == 'input' and len(plan)
+        if plan.ld_frames < self.max_columns and (not pieces or plan.pieces(
+                self.config.downsample_method).plan.ld_frames <
+                self.max_columns):
+            # (the word-piece layout is the one upload() builds: cached)
+            return None
+        room = self.max_columns - batch.LEAD - batch.TAIL
+        columns = [-(-plan.frames // batch.ALIGN) * batch.ALIGN]
+        if pieces:
+            # one piece per word, as long as the segment's longest word
+            first = np.cumsum(plan.words) - plan.words
+            longest = np.array([
+                int(np.max(plan.segment_bounds[1, f:f + n] -
+                           plan.segment_bounds[0, f:f + n])) if n else 0
+                for f, n in zip(first, plan.words)], dtype=np.int64)
+            columns.append(plan.words * (
+                -(-longest // batch.ALIGN) * batch.ALIGN))
+        columns = np.stack(columns)
+        if (columns >= room).any():
+            raise ValueError(
+                f'one segment fills {int(columns.max())} packed columns, '
+                f'more than the {room} of a pass')
+        runs, first, used = [], 0, np.zeros(len(columns), dtype=np.int64)
+        for index in range(len(plan)):
+            if (used + columns[:, index] >= room).any():
+                runs.append((first, index))
+                first, used = index, 0 * used
+            used += columns[:, index]
+        runs.append((first, len(plan)))
+        return runs
+
+    def _forward_runs(self, audio, plan, runs, tracks, features=None):
+        """forward() of a plan as the sub-plans `runs` (`sub_plans`), the
+        scores and logits gathered on the plan's own word axis.  `tracks` /
+        `features` on the plan's packed frame axis are re-packed per run."""
+        from . import batch
+        table = plan.table
+        scores = self._buffer('whole_scores', plan.ld_words)
+        logits = self._buffer('whole_logits', plan.ld_words)
+        first_word = np.cumsum(plan.words) - plan.words
+        for first, end in runs:
+            rows = slice(first, end)
+            count = end - first
+            words = plan.words[rows]
+            bounds = plan.segment_bounds[
+                :, first_word[first]:first_word[first] + int(words.sum())]
+            part = batch.Plan.from_columns(
+                np.arange(count, dtype=np.int64), plan.start_word[rows],
+                table[rows, runtime.SEG_START], table[rows, runtime.SEG_LENGTH],
+                plan.frames[rows], words, bounds,
+                table[rows, runtime.SEG_AUDIO_OFF],
+                table[rows, runtime.SEG_AUDIO_LEN])
+
+            def repack(rows):
+                """`rows` [R, plan.ld_frames] -> [R, part.ld_frames]"""
+                if rows is None:
+                    return None
+                out = torch.zeros((rows.shape[0], part.ld_frames),
+                                  dtype=rows.dtype, device=rows.device)
+                for i in range(count):
+                    at, n = int(plan.frame_off[first + i]), int(part.frames[i])
+                    to = int(part.frame_off[i])
+                    out[:, to:to + n] = rows[:, at:at + n]
+                return out
+            part_scores, part_logits = self.forward(
+                audio, part, tracks=repack(tracks), features=repack(features))
+            # the run's word columns: one block, shifted
+            at, size = int(plan.word_off[first]), part.ld_words - batch.LEAD - \
+                batch.TAIL
+            scores[at:at + size].copy_(
+                part_scores[batch.LEAD:batch.LEAD + size])
+            logits[at:at + size].copy_(
+                part_logits[batch.LEAD:batch.LEAD + size])
+        return scores, logits
+
     def _word_stage(self, wa, plan, meta, logits, scores):
         """Word embeddings -> word decoder -> output layer -> postprocess."""
         config = self.config
@@ -1307,7 +1449,8 @@ class Engine:
         layers by emph_conv1d_stack, per-word sums folded, one-launch decoder)."""
         return (self.config.downsample_location != 'input' and
                 'conv_spans' in meta and 'word_sum_tables' in meta and
-                self.fused_words and len(plan) > 0)
+                self.fused_words and len(plan) > 0 and
+                self.sub_plans(plan) is None)
 
     def forward_frames(self, audio, plan, meta):
         """The frame-rate half of forward(): features and the frame-rate layers,
@@ -1340,6 +1483,9 @@ class Engine:
         launch per kernel) and refreshes `scores` / `logits` in place.  The
         audio tensor may be refilled between replays; its address and the
         plan must not change."""
+        if self.sub_plans(plan) is not None:
+            raise ValueError('a plan past the packed-axis limit runs as '
+                             'sub-plans: it cannot be captured as one graph')
         meta = meta or self.upload(plan)
         self.timers = None
         side = torch.cuda.Stream(device=self.device)

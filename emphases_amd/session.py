@@ -649,7 +649,8 @@ class Session:
                 packed = lane.stage(audios, lengths, dtype)
             layout.seen += 1
             if tracks is None and layout.replay is None and \
-                    layout.seen >= 2 and key in lane.layouts:
+                    layout.seen >= 2 and key in lane.layouts and \
+                    engine.sub_plans(plan) is None:
                 # the layout came back: from now on one graph launch
                 layout.meta = engine.upload(plan)
                 layout.replay, layout.scores, _ = engine.capture(

@@ -20,6 +20,9 @@ Precision: float32 on CPU with the same ATen ops the reference calls
 (`torch.stft`, `conv1d`, `matmul`), autocast OFF — the reference's shipped
 bf16/fp16 autocast (`core.py:594-607`) cannot be matched to 1e-4 by anything,
 so parity is defined against its own modules in fp32.
+The model half (`forward`, `stack`, `conv_stack`, `transformer_stack`) runs in
+the dtype of its inputs: given float64 features and weights it is the float64
+reference the device paths are measured against (tests/test_gpu_paths.py).
 
 Pinning: first-party behaviour is pinned by `tests/golden/*.npz`, captured by
 importing the unmodified reference (`tests/golden/generate.py`).  Third-party
@@ -258,8 +261,12 @@ def conv_stack(x, state, prefix, layers, act):
     return x
 
 
-def positional_encoding(length, channels):
-    """transformer.py:43-48 (max_len 5000)."""
+def positional_encoding(length, channels, dtype=torch.float32):
+    """transformer.py:43-48 (max_len 5000) in `dtype`.  The table is a float32
+    buffer of the reference's module, evaluated in float32 like the weights it
+    sits next to: a float64 caller gets those float32 values, exactly (an
+    evaluation in float64 would be another model: 3.9e-4 away at position
+    5000)."""
     if length > 5000:
         raise RuntimeError('sequence exceeds the 5000-position table')
     index = torch.arange(length).unsqueeze(1)
@@ -268,7 +275,7 @@ def positional_encoding(length, channels):
     encoding = torch.zeros(length, channels)
     encoding[:, 0::2] = torch.sin(index * frequency)
     encoding[:, 1::2] = torch.cos(index * frequency)
-    return encoding
+    return encoding.to(dtype)
 
 
 def layer_norm(x, weight, bias, eps=1e-5):
@@ -285,7 +292,7 @@ def transformer_stack(x, state, prefix, layers, heads=2, valid=None):
     zero-padded word pieces of DOWNSAMPLE_LOCATION='input' have any."""
     channels, length = x.shape
     head_dim = channels // heads
-    h = x.T + positional_encoding(length, channels)            # [T, C]
+    h = x.T + positional_encoding(length, channels, x.dtype)    # [T, C]
     for i in range(layers):
         p = f'{prefix}.model.layers.{i}.'
         qkv = h @ state[p + 'self_attn.in_proj_weight'].T + \
@@ -317,7 +324,8 @@ def stack(x, state, prefix, cfg, valid=None):
             x, state, prefix, cfg.get('layers', 6),
             cfg.get('activation', 'relu'))
     return transformer_stack(
-        x, state, prefix, cfg.get('layers', 6), valid=valid)
+        x, state, prefix, cfg.get('layers', 6), cfg.get('heads', 2),
+        valid=valid)
 
 
 ###############################################################################
@@ -326,7 +334,9 @@ def stack(x, state, prefix, cfg, valid=None):
 
 
 def forward(feats, bounds, state, cfg=None, stages=None):
-    """feats [C_in, T] float32, bounds int64 [2, W] -> logits [W].
+    """feats [C_in, T], bounds int64 [2, W] -> logits [W], in the dtype of
+    `feats` (float32 restates the reference; float64 with a float64 `state`
+    is the high-precision reference of the device paths).
 
     `stages`, when a dict, receives the intermediate tensors."""
     cfg = cfg or {}
@@ -342,7 +352,8 @@ def forward(feats, bounds, state, cfg=None, stages=None):
         max_length = int(lengths.max())
         words = []
         for j in range(count):
-            piece = torch.zeros((feats.shape[0], max_length))
+            piece = torch.zeros(
+                (feats.shape[0], max_length), dtype=feats.dtype)
             piece[:, :int(lengths[j])] = feats[
                 :, int(bounds[0, j]):int(bounds[1, j])]
             embedding = stack(

@@ -317,3 +317,70 @@ def test_whole_audio_features_match_reference(seams):
         np.testing.assert_array_equal(
             seams[f'loudness/{name}'],
             seams[f'from_audio/{name}/mel_loudness'][0, 80:])
+
+
+###############################################################################
+# the float64 oracle (the high-precision reference of tests/test_gpu_paths.py)
+###############################################################################
+
+
+@pytest.mark.parametrize('heads', [1, 2, 3, 4])
+def test_float64_transformer_stack_matches_torch(heads):
+    """`oracle.transformer_stack` in float64 against torch's own
+    `nn.TransformerEncoderLayer` (post-LN, ReLU, eval) with the same weights:
+    the independent check of the oracle's head split and key-padding mask."""
+    from emphases_amd import config as cfg
+    channels, length, layers = 120, 37, 2
+    config = cfg.Config(architecture='transformer', channels=channels,
+                        heads=heads, layers=layers)
+    state = {k: torch.from_numpy(v).double()
+             for k, v in weights.random_state(config, seed=11).items()}
+    x = torch.from_numpy(synth.weights(5, (channels, length), 1.)).double()
+    modules = []
+    for i in range(layers):
+        layer = torch.nn.TransformerEncoderLayer(
+            channels, heads, dim_feedforward=channels, dropout=0.).double()
+        prefix = f'frame_encoder.model.layers.{i}.'
+        layer.load_state_dict({
+            name: state[prefix + name] for name in layer.state_dict()})
+        modules.append(layer.eval())
+    for valid in (None, length, 23, 1):
+        got = oracle.transformer_stack(
+            x, state, 'frame_encoder', layers, heads, valid=valid)
+        assert got.dtype == torch.float64
+        h = (x.T + oracle.positional_encoding(
+            length, channels, torch.float64))[:, None]        # [T, 1, C]
+        mask = None
+        if valid is not None:
+            mask = torch.arange(length)[None] >= valid
+        for layer in modules:
+            h = layer(h, src_key_padding_mask=mask)
+        assert torch.abs(got - h[:, 0].T).max() < 1e-12, (heads, valid)
+    # the oracle's `stack` hands the configuration's heads through
+    got = oracle.stack(x, state, 'frame_encoder', dict(
+        architecture='transformer', layers=layers, heads=heads))
+    want = oracle.transformer_stack(x, state, 'frame_encoder', layers, heads)
+    assert torch.equal(got, want)
+
+
+def test_float64_oracle_matches_variant_goldens(variants):
+    """The oracle upcast to float64 (features, weights, word pieces,
+    positional encoding) on every variant: within 1e-5 x scale of the
+    float32 goldens - the upcast changed no arithmetic, only its precision."""
+    audio = torch.from_numpy(synth.pcm_to_float(variants['audio_pcm']))
+    bounds = variants['bounds_frames'].astype(np.int64)
+    padded = torch.nn.functional.pad(audio, (432, 432))
+    checked = 0
+    for name in variants['names']:
+        config, overrides = variant_config(name)
+        state = {k: torch.from_numpy(v).double() for k, v in
+                 variant_state(variants, name, config).items()}
+        feats = oracle.features(
+            padded[:, :audio.shape[1]], overrides, synth.pitch_tracks)[0]
+        logits = oracle.forward(feats.double(), bounds, state, overrides)
+        assert logits.dtype == torch.float64
+        want = variants[f'{name}/logits']
+        scale = float(np.abs(want).max())
+        assert np.abs(logits.numpy() - want).max() < 1e-5 * scale, name
+        checked += 1
+    assert checked == 39
