@@ -41,11 +41,19 @@ def parse_args():
         help='f32 (default), or an opt-in precision: fp32 operands split '
              'into bf16 pieces on the bf16 matrix pipe, fp32 accumulation '
              '(scores within 1e-5 of f32)')
+    # (an addition too: the reference reads METHOD from a --config file)
+    parser.add_argument(
+        '--method', choices=emphases_amd.config.METHODS,
+        help="the emphasis annotation method: 'neural' (default, the model) "
+             'or a baseline')
     return parser.parse_args()
 
 
 def main():
     arguments = vars(parse_args())
+    method = arguments.pop('method')
+    if method is not None:
+        emphases_amd.configure(method=method)
     if int(os.environ.get('WORLD_SIZE', 1)) <= 1:
         emphases_amd.from_files_to_files(**arguments)
         return

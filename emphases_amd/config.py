@@ -37,6 +37,8 @@ ARCHITECTURES = ('convolution', 'transformer')
 DOWNSAMPLE_LOCATIONS = ('input', 'intermediate', 'inference', 'loss')
 DOWNSAMPLE_METHODS = ('sum', 'average', 'max', 'center')
 LOSSES = ('bce', 'mse')
+# Emphasis annotation methods (defaults.py:211, dispatch core.py:244-287)
+METHODS = ('neural', 'pitch-variance', 'duration-variance', 'prominence')
 
 
 @dataclasses.dataclass(frozen=True)
@@ -62,8 +64,15 @@ class Config:
     # Transformer constants (transformer.py:18-23)
     heads: int = 2
     layer_norm_eps: float = 1e-5
+    # Emphasis annotation method (defaults.py:211): the model, or one of the
+    # paper's baselines (`baselines/`), which build no model at all
+    method: str = 'neural'
 
     def __post_init__(self):
+        if self.method not in METHODS:
+            # core.py:286-287
+            raise ValueError(
+                f'Emphasis annotation method {self.method} is not defined')
         if self.architecture not in ARCHITECTURES:
             # layers/__init__.py:13-14
             raise ValueError(

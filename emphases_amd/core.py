@@ -149,7 +149,15 @@ def from_alignments_and_audios(alignments, audios, sample_rate=cfg.SAMPLE_RATE,
         default: `penn` itself, if installed.
     precision: 'f32' (default), or 'bf16x3' / 'bf16x3_fast' / 'bf16x6'
         (`engine.PRECISIONS`).
+    config.method (or the active configuration's): a baseline other than
+        'neural' runs `baselines` instead of the model (`core.py:244-287`);
+        `checkpoint`, `batch_size`, `conv_tile` and `precision` do not apply.
     Returns a list of float32 tensors [1, W_i] (CPU if `gpu is None`)."""
+    method = (config or active_config()).method
+    if method != 'neural':
+        from . import baselines
+        return baselines.from_alignments_and_audios(
+            method, alignments, audios, sample_rate, gpu, pitch_tracker)
     session = get_session(checkpoint, gpu, config, conv_tile, precision)
     return session.run(
         alignments, audios, sample_rate, batch_size,
@@ -157,7 +165,8 @@ def from_alignments_and_audios(alignments, audios, sample_rate=cfg.SAMPLE_RATE,
 
 
 def from_alignment_and_audio(alignment, audio, sample_rate, checkpoint=None,
-                             batch_size=None, gpu=None, precision='f32'):
+                             batch_size=None, gpu=None, precision='f32', *,
+                             pitch_tracker=None):
     """Produce emphasis scores for each word (`core.py:223-265`).
 
     alignment: object with `len()`, `[i]` -> word with `.start()/.end()/
@@ -168,11 +177,14 @@ def from_alignment_and_audio(alignment, audio, sample_rate, checkpoint=None,
         the reference.
     precision: 'f32' (default), or one of the opt-in split-bf16 names of
         `engine.PRECISIONS` (an addition; every entry point below takes it).
+    pitch_tracker: as in `from_alignments_and_audios` (keyword only, an
+        addition; every entry point below takes it).
+    The active configuration's `method` picks the model or a baseline.
     Returns float32 scores [1, W]; words of chunks the reference drops
     (`core.py:414-415`) have no score, as there."""
     return from_alignments_and_audios(
         [alignment], [audio], sample_rate, checkpoint, batch_size, gpu,
-        precision=precision)[0]
+        precision=precision, pitch_tracker=pitch_tracker)[0]
 
 
 def from_text_and_audio(text, audio, sample_rate, checkpoint=None,
@@ -186,7 +198,7 @@ def from_text_and_audio(text, audio, sample_rate, checkpoint=None,
 
 
 def from_file(text_file, audio_file, checkpoint=None, batch_size=None,
-              gpu=None, precision='f32'):
+              gpu=None, precision='f32', *, pitch_tracker=None):
     """`core.py:23-73`: scores for an alignment file (.TextGrid / .json) and
     an audio file."""
     if not str(text_file).endswith(('.TextGrid', '.json')):
@@ -199,7 +211,7 @@ def from_file(text_file, audio_file, checkpoint=None, batch_size=None,
     samples, rate = load.wav(audio_file, raw=True)
     return from_alignment_and_audio(
         alignment_module.Alignment(text_file), samples, rate, checkpoint,
-        batch_size, gpu, precision)
+        batch_size, gpu, precision, pitch_tracker=pitch_tracker)
 
 
 def _save(alignment, scores, output_prefix):
@@ -210,19 +222,19 @@ def _save(alignment, scores, output_prefix):
 
 def from_file_to_file(text_file, audio_file, output_prefix=None,
                       checkpoint=None, batch_size=None, gpu=None,
-                      precision='f32'):
+                      precision='f32', *, pitch_tracker=None):
     """`core.py:76-112`"""
     from pathlib import Path
     if output_prefix is None:
         output_prefix = Path(text_file).stem
     scores = from_file(text_file, audio_file, checkpoint, batch_size, gpu,
-                       precision)
+                       precision, pitch_tracker=pitch_tracker)
     _save(alignment_module.Alignment(text_file), scores, output_prefix)
 
 
 def files_to_scores(text_files, audio_files, session, batch_size=None,
                     utterances_per_batch=256, deliver=None,
-                    deliver_batch=None):
+                    deliver_batch=None, pitch_tracker=None):
     """The loop of `core.py:169-179` over ragged batches of
     `utterances_per_batch` files, two batches in flight.  A batch of files is
     opened by the library in one call (`files.FileBatch`: TextGrids parsed and
@@ -239,7 +251,8 @@ def files_to_scores(text_files, audio_files, session, batch_size=None,
         if not str(file).endswith(('.TextGrid', '.json')):
             from_text_and_audio(None, None, None)
     _files_to_scores(text_files, audio_files, session, batch_size,
-                     utterances_per_batch, deliver, deliver_batch)
+                     utterances_per_batch, deliver, deliver_batch,
+                     pitch_tracker)
 
 
 # `files_to_scores` appends (stage, batch, start, end) in perf_counter_ns here when
@@ -253,7 +266,8 @@ def _stamp(stage, position, start):
 
 
 def _files_to_scores(text_files, audio_files, session, batch_size,
-                     utterances_per_batch, deliver, deliver_batch):
+                     utterances_per_batch, deliver, deliver_batch,
+                     pitch_tracker=None):
     """Three stages run side by side, each on a thread of its own (what the
     helpers call are library or numpy routines that leave the interpreter lock
     alone; none of them enters a torch CPU parallel region):
@@ -407,7 +421,8 @@ def _files_to_scores(text_files, audio_files, session, batch_size,
             jobs = [(position,
                      session.submit_staged(plan, audios)
                      if type(audios) is session_module.Staged else
-                     session.submit(picked, audios, rate, batch_size, plan=plan),
+                     session.submit(picked, audios, rate, batch_size, plan=plan,
+                                    pitch_tracker=pitch_tracker),
                      opened, chosen, range(first + chosen[0], first + chosen[-1] + 1)
                      if type(chosen) is range else [first + i for i in chosen])
                     for rate, chosen, picked, audios, plan in groups]
@@ -441,23 +456,37 @@ def _files_to_scores(text_files, audio_files, session, batch_size,
 def from_files_to_files(text_files, audio_files, output_prefixes=None,
                         checkpoint=None, batch_size=None, gpu=None,
                         utterances_per_batch=256, conv_tile=None,
-                        precision='f32'):
+                        precision='f32', *, pitch_tracker=None):
     """`core.py:115-179`, but the files are processed in ragged batches of
     `utterances_per_batch` instead of one at a time, two batches in flight,
     read, parsed and written by the library's host threads
     (`files_to_scores`).  On several GPUs: `dist.from_files_to_files`.
     `precision`: 'f32' or an opt-in name of `engine.PRECISIONS`; the scores
-    of a file are bitwise those of the tensor API at the same precision."""
+    of a file are bitwise those of the tensor API at the same precision.
+    Under a baseline `method` of the active configuration the files are
+    scored by `baselines.files_to_scores` (no model)."""
     from pathlib import Path
     text_files, audio_files = list(text_files), list(audio_files)
     if output_prefixes is None:
         output_prefixes = [Path(file).stem for file in text_files]
     output_prefixes = list(output_prefixes)
+
+    def deliver_batch(opened, chosen, indices, scores):
+        opened.write(chosen, [output_prefixes[i] for i in indices], scores)
+    method = active_config().method
+    if method != 'neural':
+        from . import baselines
+        for file in text_files:
+            if not str(file).endswith(('.TextGrid', '.json')):
+                from_text_and_audio(None, None, None)
+        baselines.files_to_scores(
+            method, text_files, audio_files, gpu, utterances_per_batch,
+            deliver_batch, pitch_tracker)
+        return
     session = get_session(checkpoint, gpu, None, conv_tile, precision)
     files_to_scores(
         text_files, audio_files, session, batch_size, utterances_per_batch,
-        deliver_batch=lambda opened, chosen, indices, scores: opened.write(
-            chosen, [output_prefixes[i] for i in indices], scores))
+        deliver_batch=deliver_batch, pitch_tracker=pitch_tracker)
 
 
 ###############################################################################

@@ -320,7 +320,7 @@ def from_files_to_files(text_files, audio_files, output_prefixes=None,
                         checkpoint=None, batch_size=None, config=None,
                         group=None, utterances_per_batch=256,
                         conv_tile=CONV_TILE, gather=True, compute=None,
-                        precision='f32'):
+                        precision='f32', *, pitch_tracker=None):
     """`emphases.from_files_to_files` (`core.py:115-179`) over the ranks of a
     process group, one process per GPU.  No rank reads what it does not
     compute:
@@ -346,7 +346,10 @@ def from_files_to_files(text_files, audio_files, output_prefixes=None,
     all_gather.  The files a rank writes are bitwise those a single process
     writes (`core.from_files_to_files`, the single-process command line): the
     kernel family does not depend on the batch (`Engine.frame_tile`).  `compute(text_files, audio_files, deliver)` replaces
-    step 3's engine (the gloo CPU test passes the oracle)."""
+    step 3's engine (the gloo CPU test passes the oracle).  A baseline
+    `method` (of `config`, else of the active configuration) scores every
+    word of a file through `baselines.files_to_scores` instead of the model;
+    `pitch_tracker` is handed on as in `core.from_files_to_files`."""
     from pathlib import Path
     from . import alignment as alignment_module
     from . import batch
@@ -366,6 +369,8 @@ def from_files_to_files(text_files, audio_files, output_prefixes=None,
         output_prefixes = [Path(file).stem for file in text_files]
     output_prefixes = list(output_prefixes)
     architecture = getattr(config, 'architecture', 'convolution')
+    from . import core
+    method = (config or core.active_config()).method
     headers = [load.wav_info(file) for file in audio_files]
     frames = [frames_at_16k(samples, rate) for rate, _, samples in headers]
     shards = assign(cost(frames, architecture), world)
@@ -387,9 +392,13 @@ def from_files_to_files(text_files, audio_files, output_prefixes=None,
             for lo in range(0, len(own_text), 1024):
                 opened = files.FileBatch(
                     own_text[lo:lo + 1024], own_audio[lo:lo + 1024])
-                counts.extend(batch.score_counts(
-                    opened.all_times(), lengths[lo:lo + 1024],
-                    batch_size).tolist())
+                if method != 'neural':
+                    # (a baseline scores every word)
+                    counts.extend(len(t) for t in opened.all_times())
+                else:
+                    counts.extend(batch.score_counts(
+                        opened.all_times(), lengths[lo:lo + 1024],
+                        batch_size).tolist())
                 opened.close()
         except Exception as error:       # noqa: BLE001
             failure = error
@@ -405,18 +414,24 @@ def from_files_to_files(text_files, audio_files, output_prefixes=None,
         if compute is not None:
             compute(own_text, own_audio, deliver)
         elif mine:
-            from . import core
-            session = core.get_session(
-                checkpoint, gpu, config, conv_tile, precision)
             def deliver_batch(opened, chosen, indices, scores):
                 opened.write(
                     chosen, [output_prefixes[mine[i]] for i in indices],
                     scores)
                 for index, item in zip(indices, scores):
                     local[mine[index]] = item
-            core.files_to_scores(
-                own_text, own_audio, session, batch_size, utterances_per_batch,
-                deliver_batch=deliver_batch)
+            if method != 'neural':
+                from . import baselines
+                baselines.files_to_scores(
+                    method, own_text, own_audio, gpu, utterances_per_batch,
+                    deliver_batch, pitch_tracker)
+            else:
+                session = core.get_session(
+                    checkpoint, gpu, config, conv_tile, precision)
+                core.files_to_scores(
+                    own_text, own_audio, session, batch_size,
+                    utterances_per_batch, deliver_batch=deliver_batch,
+                    pitch_tracker=pitch_tracker)
     except Exception as error:       # noqa: BLE001
         if not gather:
             raise

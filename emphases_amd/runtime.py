@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -30,6 +30,7 @@ ACTIVATIONS = {None: 0, 'none': 0, 'relu': 1, 'gelu': 2, 'silu': 3,
 REDUCTIONS = {'sum': 0, 'average': 1, 'max': 2, 'center': 3}
 POSTPROCESS = {None: 0, 'bce': 1, 'mse': 2}
 AUDIO_F32, AUDIO_PCM16 = 0, 1
+SPREAD_IDENTITY, SPREAD_LOG2 = 0, 1
 (METRIC_COUNT, METRIC_BCE, METRIC_SQUARED_ERROR, METRIC_COVARIANCE,
  METRIC_SUM_PREDICTED, METRIC_SUMSQ_PREDICTED, METRIC_SUM_TARGET,
  METRIC_SUMSQ_TARGET, METRIC_FIELDS) = range(9)
@@ -182,6 +183,8 @@ SIGNATURES = {
         _ptr, _ptr, _ptr, _i64, _i32, _f32, _f32, _ptr, _ptr]),
     'emph_add_layernorm': (_c.c_int, [
         _ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _f32, _i64, _i64, _ptr]),
+    'emph_quantile_spreads': (_c.c_int, [
+        _ptr, _i64, _ptr, _i64, _i32, _ptr, _ptr, _ptr, _i64, _ptr]),
 }
 
 _library = None

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 30
+#define EMPH_ABI_VERSION 31
 
 /* Segment-table fields */
 enum {
@@ -872,6 +872,44 @@ int emph_word_metrics(const float* logits, const float* targets,
                       const int32_t* word_segment, int64_t total, int32_t post,
                       float predicted_mean, float target_mean,
                       double* accumulators, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* Baselines                                                                 */
+/* ------------------------------------------------------------------------ */
+
+/* What emph_quantile_spreads selects over */
+enum {
+    EMPH_SPREAD_IDENTITY = 0,   /* the values as they are                      */
+    EMPH_SPREAD_LOG2 = 1        /* log2f of each value (pitch in Hz)           */
+};
+
+/* Exact quantile spreads of segments of a packed float32 axis, and the
+ * zero-centred pitch-variance scores, for a whole ragged batch in two launches.
+ *
+ * Replaces the loop of emphases/baselines/pitch_variance/core.py:27-43:
+ * torch.log2(pitch), spread(x) = torch.quantile(x, .95) - torch.quantile(x, .05)
+ * (core.py:51-53) over the whole utterance and over pitch[0, start:end] of every
+ * word, torch.tensor(word_spreads) - utterance_spread.  The quantiles are
+ * BITWISE those of torch.quantile on the CPU for the same float32 values
+ * (exact selection, ATen's rank and fused lerp; a segment with a NaN gives
+ * NaN; -0 and +0 are one value).
+ *
+ *   values    float32 [ld]        packed axis (pitch rows back to back)
+ *   segments  int64 [n_segments][3] = (first column, columns >= 1, row of the
+ *                                 segment whose spread is subtracted, or -1);
+ *                                 the caller refuses empty segments (torch's
+ *                                 "quantile() input tensor must be non-empty")
+ *   transform EMPH_SPREAD_*
+ *   stats     float32 [n_segments][3] = (quantile .05, quantile .95, spread)
+ *   selected  float32 [ld] or NULL: the (transformed) values of every segment
+ *                                 whose third field is -1, as selected over
+ *   out       float32 [n_rows]    spread of row i - spread of the row it names,
+ *                                 for rows 0 .. n_rows - 1 (n_rows 0: one launch)
+ */
+int emph_quantile_spreads(const float* values, int64_t ld, const int64_t* segments,
+                          int64_t n_segments, int32_t transform, float* stats,
+                          float* selected, float* out, int64_t n_rows,
+                          void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* The whole convolutional path in one call                                  */
