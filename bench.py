@@ -21,12 +21,15 @@ region is the one reported (`ms_per_step`, `value`), with the fastest and the
 slowest beside it.
 
 Prints ONE JSON line on rank 0 with BASELINE.json's metric (utterances/s,
-whole job), the roofline of the dominant kernel (fp32-MFMA conv1d, measured
-live with HIP events on the launch stream, the committed rocprofv3 average
-beside it), the CPU oracle timed on the host cores (threads AND one process
-per core), and — on one GPU — side records for BASELINE configs[2]
-(Transformer), configs[3] (10 k-utterance corpus) and configs[4] (5-minute
-utterances chunked at batch_size 3000) and the public API end to end.
+whole job).  A plain run does only what that figure needs: it sets up, warms
+up, times the steps, writes its outputs (`--dump-outputs`) and prints the
+line.  `--full` adds everything else: the roofline of the dominant kernel
+(fp32-MFMA conv1d, measured live with HIP events on the launch stream, the
+committed rocprofv3 average beside it) and the per-kernel times, the CPU
+oracle timed on the host cores (threads AND one process per core), and — on
+one GPU — side records for BASELINE configs[2] (Transformer), configs[3]
+(10 k-utterance corpus) and configs[4] (5-minute utterances chunked at
+batch_size 3000), the opt-in precisions and the public API end to end.
 
 `--workload corpus | longform` is the STRONG-scaling mode for BASELINE
 configs[3] / configs[4]: the whole job (10 000 utterances of 2-30 s, or 64
@@ -35,7 +38,7 @@ by `dist.assign` (LPT by frames), every rank keeps the audio of ITS shard
 resident, and one step = one whole job = `dist.exchange_counts` (collective 1)
 -> the shard's forward (hipGraph replay) -> `dist.exchange_scores` (collective
 2: every rank ends with all scores in input order), both collectives inside
-the timed region.  With N > 1 ranks the default line carries both modes as
+the timed region.  With N > 1 ranks the `--full` line carries both modes as
 side records (`configs_3_corpus_sharded`, `configs_4_longform_sharded`).
 `--gpus N` without a torchrun environment starts the N workers itself.
 
@@ -107,11 +110,21 @@ def parse_args():
     parser.add_argument('--corpus-utterances', type=int, default=10000)
     parser.add_argument('--longform-utterances', type=int, default=64)
     parser.add_argument('--tile', type=int, default=None)
-    parser.add_argument('--no-cpu-baseline', action='store_true')
+    parser.add_argument('--full', action='store_true',
+                        help='measure beyond the headline: the CPU baseline, '
+                             'the per-kernel times and roofline of the '
+                             'dominant kernel, and the side records (the '
+                             'public API, the opt-in precisions, configs[2], '
+                             '[3], [4]).  Without it a run sets up, warms up, '
+                             'times the steps and prints the line')
+    parser.add_argument('--no-cpu-baseline', action='store_true',
+                        help='with --full: skip the CPU baseline')
     parser.add_argument('--no-api', action='store_true',
-                        help='skip the end-to-end public-API measurement')
+                        help='with --full: skip the end-to-end public-API '
+                             'measurement')
     parser.add_argument('--no-side', action='store_true',
-                        help='skip the side records (configs[2], [3], [4])')
+                        help='with --full: skip the side records (configs[2], '
+                             '[3], [4])')
     parser.add_argument('--streams', type=int, default=2,
                         help='batches in flight: consecutive steps alternate '
                              'between this many HIP streams (each with its '
@@ -1501,10 +1514,11 @@ def sharded_job(workload, args, rank, world, device, steps, warmup, regions,
     torch.distributed.all_reduce(highest, op=torch.distributed.ReduceOp.MAX)
     assert float(lowest) == float(highest), 'ranks hold different scores'
     assert int(sizes.sum()) == int(np.asarray(all_counts).sum())
-    # the compute alone (no collectives), this rank, same protocol
+    # the compute alone (no collectives), this rank, same protocol, and the
+    # per-kernel times (`kernel_passes` 0: neither, the job's rate alone)
     compute_ms = None
     kernels, passes = {}, kernel_passes
-    if runner is not None:
+    if runner is not None and kernel_passes:
         torch.cuda.synchronize()
         start = time.perf_counter()
         for _ in range(steps):
@@ -1514,10 +1528,12 @@ def sharded_job(workload, args, rank, world, device, steps, warmup, regions,
         kernels, passes = runner.kernel_times(kernel_passes)
         if 'conv_spans' in runner.meta:
             kernels['_stack_spans'] = runner.meta['conv_spans'][1] // 8
-    compute = torch.tensor([compute_ms or 0.], dtype=torch.float64,
-                           device=wire)
-    every = torch.zeros(world, dtype=torch.float64, device=wire)
-    torch.distributed.all_gather_into_tensor(every, compute)
+    every = None
+    if kernel_passes:
+        compute = torch.tensor([compute_ms or 0.], dtype=torch.float64,
+                               device=wire)
+        every = torch.zeros(world, dtype=torch.float64, device=wire)
+        torch.distributed.all_gather_into_tensor(every, compute)
     line = summary(laps, steps)
     seconds = line['timed_region_s'] / steps
     loads = [int(frames[s].sum()) for s in shards]
@@ -1533,11 +1549,12 @@ def sharded_job(workload, args, rank, world, device, steps, warmup, regions,
         'scores': total_words, 'checksum': float(checksum.item()),
         'frames_per_rank': loads,
         'lpt_imbalance': max(loads) / (sum(loads) / len(loads)),
-        'compute_only_ms_per_rank': [float(v) for v in every.tolist()],
-        'collectives_and_reorder_ms':
-            seconds * 1e3 - float(every.max().item()),
         'mfma_frac_per_gpu': line['mfma_frac'] / world,
         'memory_allocated_GB': torch.cuda.max_memory_allocated() / 1e9})
+    if every is not None:
+        line['compute_only_ms_per_rank'] = [float(v) for v in every.tolist()]
+        line['collectives_and_reorder_ms'] = \
+            seconds * 1e3 - float(every.max().item())
     line['mfma_frac'] = line.pop('mfma_frac_per_gpu')
     line['hbm_frac_compulsory'] /= world
     del runner
@@ -1788,13 +1805,13 @@ def main():
                  'and bench.py starts the workers itself')
     sharded = args.workload != 'batch'
 
-    # The host baseline first: its child processes are started before this
-    # process has touched the GPU, and nothing else competes for the cores.
-    # Rank 0 runs it at EVERY world size and workload (an N > 1 or
+    # With --full, the host baseline first: its child processes are started
+    # before this process has touched the GPU, and nothing else competes for
+    # the cores.  Rank 0 runs it at EVERY world size and workload (an N > 1 or
     # strong-scaling line without it reads as unmeasured); the other ranks wait
     # for rank 0 inside init_process_group, idle.
     host = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         host = guarded(cpu_baseline)
 
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
@@ -1824,15 +1841,12 @@ def run_sharded(args, rank, world, device, host):
     job."""
     line, kernels, passes, outputs = sharded_job(
         args.workload, args, rank, world, device, args.steps, args.warmup,
-        args.regions)
+        args.regions, kernel_passes=3 if args.full else 0)
     if rank != 0:
         return
     if args.dump_outputs:
         # (every rank holds the whole job's scores; rank 0 writes them)
         dump_outputs(args.dump_outputs, outputs)
-    roof, committed = roofline(
-        kernels, passes, None, 'conv', spans=kernels.pop('_stack_spans', None),
-        layers=1 + cfg.DEFAULT.layers)
     unit = 'utterances/s'
     result = {
         'metric': 'utterances/s (mixed 2-30 s @16 kHz) whole-node'
@@ -1852,8 +1866,12 @@ def run_sharded(args, rank, world, device, host):
                                '(score counts, padded scores), both inside '
                                'the timed region'},
         'frames_per_s_per_gpu': line['frames_per_s'] / world,
-        'roofline': roof, 'from_profiles': committed,
         'job': line}
+    if args.full:
+        result['roofline'], result['from_profiles'] = roofline(
+            kernels, passes, None, 'conv',
+            spans=kernels.pop('_stack_spans', None),
+            layers=1 + cfg.DEFAULT.layers)
     if host is not None:
         result['cpu_baseline'] = host
     emit(result, args)
@@ -1918,8 +1936,10 @@ def run_batch(args, rank, world, device, host):
     elapsed = line['timed_region_s']
 
     # Dominant kernel, timed live with HIP events on the launch stream
-    runner.after = None
-    kernels, passes = runner.kernel_times(20)
+    kernels = passes = None
+    if args.full:
+        runner.after = None
+        kernels, passes = runner.kernel_times(20)
     checksum = float(scores[columns].sum().item())
     headline_scores = scores[columns].clone()
     meta_tile, lanes = runner.meta['tile'], len(runner.lanes)
@@ -1933,7 +1953,7 @@ def run_batch(args, rank, world, device, host):
     # strong-scaled through dist.assign + the two collectives (every rank
     # takes part; a failure on one rank raises on all of them, see dist.py).
     sharded = {}
-    if world > 1 and args.config == 'conv' and not args.no_side:
+    if world > 1 and args.config == 'conv' and args.full and not args.no_side:
         for name, workload_name in (('configs_3_corpus_sharded', 'corpus'),
                                     ('configs_4_longform_sharded', 'longform')):
             try:
@@ -1945,9 +1965,6 @@ def run_batch(args, rank, world, device, host):
                 sharded[name] = {'error': repr(error)}
 
     if rank == 0:
-        roof, committed = roofline(
-            kernels, passes, line['ms_per_step'], args.config,
-            spans=stack_spans, layers=frame_layers, precision=args.precision)
         total_utterances = UTTERANCES * world
         result = {
             'metric': 'utterances/s (10 s @16 kHz) whole-node',
@@ -1986,8 +2003,6 @@ def run_batch(args, rank, world, device, host):
                 f'one {args.backend} all_gather of the {args.steps} steps\' '
                 'per-word scores at the end of each timed region'},
             'frames_per_s_per_gpu': plan.total_frames * args.steps / elapsed,
-            'roofline': roof,
-            'from_profiles': committed,
             # the whole path against both ceilings (per GPU).
             # The conv path is MFMA-bound: its compulsory HBM traffic is only
             # 641 B per frame.
@@ -1998,28 +2013,37 @@ def run_batch(args, rank, world, device, host):
                 'hbm_frac_compulsory': plan.total_frames * BYTES_PER_FRAME *
                                        args.steps / elapsed / PEAK_HBM,
                 'binds': 'mfma'} if args.config == 'conv' else None,
-            # NOT a decomposition of ms_per_step: these are HIP-event times of
-            # eager launches on ONE stream (each pair brackets its dispatch
-            # gap), while the step replays a graph with two batches in
-            # flight, whose kernels overlap - the sum is larger than the step.
-            'kernels_us_per_step': {
-                name: value[3] / passes * 1e6
-                for name, value in kernels.items()},
-            'kernels_us_per_step_events': {
-                name: value[1] / passes * 1e6
-                for name, value in kernels.items()},
-            'kernels_us_per_step_is': (
-                'eager launches, one stream: kernel-exact (emph_launch_timer) '
-                'and between recorded HIP events (incl. dispatch gap); the '
-                'step itself is a two-lane graph replay with overlapping '
-                'kernels'),
-            'kernels_us_rocprof': rocprof_kernels(args.config),
         }
+        if kernels is not None:
+            roof, committed = roofline(
+                kernels, passes, line['ms_per_step'], args.config,
+                spans=stack_spans, layers=frame_layers,
+                precision=args.precision)
+            result.update({
+                'roofline': roof,
+                'from_profiles': committed,
+                # NOT a decomposition of ms_per_step: these are HIP-event
+                # times of eager launches on ONE stream (each pair brackets
+                # its dispatch gap), while the step replays a graph with two
+                # batches in flight, whose kernels overlap - the sum is larger
+                # than the step.
+                'kernels_us_per_step': {
+                    name: value[3] / passes * 1e6
+                    for name, value in kernels.items()},
+                'kernels_us_per_step_events': {
+                    name: value[1] / passes * 1e6
+                    for name, value in kernels.items()},
+                'kernels_us_per_step_is': (
+                    'eager launches, one stream: kernel-exact '
+                    '(emph_launch_timer) and between recorded HIP events '
+                    '(incl. dispatch gap); the step itself is a two-lane '
+                    'graph replay with overlapping kernels'),
+                'kernels_us_rocprof': rocprof_kernels(args.config)})
         result['checksum'] = checksum
         result.update(sharded)
         if host is not None:
             result['cpu_baseline'] = host
-        if world == 1 and args.config == 'conv':
+        if world == 1 and args.config == 'conv' and args.full:
             if not args.no_api:
                 result['end_to_end_api'] = guarded(
                     end_to_end_api, audios, alignments)

@@ -95,12 +95,13 @@ def test_more_ranks_than_utterances(tmp_path):
 
 @pytest.mark.timeout(900)
 def test_bench_with_two_ranks(tmp_path):
-    """`bench.py --gpus 2` the way the driver launches it (one process per
-    rank, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) with
-    the gloo backend, both ranks on the one GPU of the box: rank 0 prints ONE
-    JSON line whose value is the whole job's rate (128 utterances per step),
-    the closing all_gather returns every rank's own rows intact (asserted
-    inside bench.py), and the other rank prints nothing."""
+    """`bench.py --gpus 2 --full` the way the driver launches it (one process
+    per rank, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment)
+    with the gloo backend, both ranks on the one GPU of the box: rank 0 prints
+    ONE JSON line whose value is the whole job's rate (128 utterances per
+    step) with the roofline beside it, the closing all_gather returns every
+    rank's own rows intact (asserted inside bench.py), and the other rank
+    prints nothing."""
     import json
     port = _free_port()
     children = []
@@ -110,7 +111,7 @@ def test_bench_with_two_ranks(tmp_path):
                    MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY='0')
         children.append(subprocess.Popen(
             [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
-             '--steps', '6', '--warmup', '2', '--backend', 'gloo',
+             '--steps', '6', '--warmup', '2', '--backend', 'gloo', '--full',
              '--no-cpu-baseline', '--no-api'],
             env=env, cwd=ROOT, stdout=subprocess.PIPE, text=True))
     outputs = [child.communicate(timeout=600)[0] for child in children]
@@ -149,14 +150,14 @@ def _bench(arguments, world, backend=None, timeout=900):
 
 @pytest.mark.timeout(1200)
 def test_bench_strong_scaling_modes(tmp_path):
-    """`bench.py --workload corpus | longform` (BASELINE configs[3] / [4]
-    strong-scaled): the whole job sharded by dist.assign, both collectives
+    """`bench.py --workload corpus | longform --full` (BASELINE configs[3] /
+    [4] strong-scaled): the whole job sharded by dist.assign, both collectives
     inside the timed region.  One rank under nccl (= RCCL) and two gloo ranks
     sharing the box's one GPU must report the SAME job - same utterances,
     frames, scores and checksum (all scores on every rank, input order) -
     and the two-rank line names its shards."""
     import json
-    common = ['--steps', '3', '--warmup', '1', '--regions', '2',
+    common = ['--steps', '3', '--warmup', '1', '--regions', '2', '--full',
               '--no-cpu-baseline']
     for workload, extra, utterances in (
             ('corpus', ['--corpus-utterances', '600'], 600),
@@ -234,6 +235,52 @@ def test_bench_dump_outputs_are_the_api_scores(tmp_path):
         alignments, [torch.from_numpy(a) for a in audios], gpu=0)
     want = torch.cat([w.reshape(-1).cpu() for w in want]).numpy()
     assert np.abs(first['scores'] - want).max() < 1e-5
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1` without `--full`: the line carries the headline -
+    metric, value (64 utterances per step over ms_per_step), unit, dtype - and
+    nothing measured beside it: no CPU baseline, no roofline or per-kernel
+    times, no side record in the line or in the side-records file.  The same
+    holds for a strong-scaling line (`--workload corpus`): its job, no
+    compute-only pass."""
+    import json
+    side = tmp_path / 'side.json'
+    child = subprocess.run(
+        [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1',
+         '--steps', '3', '--warmup', '1', '--regions', '1', '--no-preroll',
+         '--side-records', str(side)],
+        cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert child.returncode == 0, child.stderr[-3000:]
+    lines = [l for l in child.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line['metric'] == 'utterances/s (10 s @16 kHz) whole-node'
+    assert line['unit'] == 'utterances/s' and line['dtype'] == 'f32'
+    assert line['higher_is_better'] is True and line['steps'] == 3
+    assert abs(line['value'] - 64 / (line['ms_per_step'] * 1e-3)) \
+        < 1e-6 * line['value']
+    for key in ('roofline', 'cpu_baseline', 'job'):
+        assert key not in line, key
+    assert 'failed' not in line.get('side', {})
+    full = json.loads(side.read_text())
+    for key in ('roofline', 'from_profiles', 'kernels_us_per_step',
+                'cpu_baseline', 'end_to_end_api', 'single_utterance_api',
+                'configs_1_conv_bf16x3', 'files_api', 'configs_2_transformer',
+                'configs_3_corpus', 'configs_4_longform'):
+        assert key not in full, key
+    (corpus,) = _bench(['--workload', 'corpus', '--corpus-utterances', '600',
+                        '--steps', '3', '--warmup', '1', '--regions', '1',
+                        '--side-records', str(side)], 1, timeout=300)
+    assert len(corpus) == 1
+    corpus = json.loads(corpus[0])
+    assert corpus['scaling'] == 'strong' and corpus['job']['utterances'] == 600
+    assert abs(corpus['value'] - 600 / (corpus['ms_per_step'] * 1e-3)) \
+        < 1e-6 * corpus['value']
+    for key in ('roofline', 'cpu_baseline'):
+        assert key not in corpus, key
+    assert 'compute_only_ms_per_rank' not in corpus['job']
 
 
 @pytest.mark.timeout(900)

@@ -1599,6 +1599,21 @@ def test_bench_line_stays_under_the_driver_limit(tmp_path, monkeypatch):
         os.path.join(ROOT, 'bench_side.json')
 
 
+def test_bench_full_is_opt_in(monkeypatch):
+    """A plain `bench.py` run measures the headline alone; the CPU baseline,
+    the per-kernel times and the side records wait for `--full`, which the
+    `--no-*` options then trim."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, 'argv', [
+        'bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert not bench.parse_args().full
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-side'])
+    args = bench.parse_args()
+    assert args.full and args.no_side and not args.no_api
+
+
 def test_bench_dump_outputs(tmp_path, monkeypatch):
     """`bench.py --dump-outputs DIR`: one .npy per array, float32 or float64
     (integers exactly, as float64); over the size limit every array keeps the

@@ -9,7 +9,7 @@ cd $repo
 for lap in 1 2 3; do
   for mode in "32 0" "16 1"; do
     set -- $mode
-    EMPHASES_SPLIT_TILE=$1 EMPHASES_FUSE_QKV=$2 python3 bench.py --config transformer --precision bf16x3 --steps 50 --warmup 5 \
+    EMPHASES_SPLIT_TILE=$1 EMPHASES_FUSE_QKV=$2 python3 bench.py --full --config transformer --precision bf16x3 --steps 50 --warmup 5 \
         --no-cpu-baseline --no-side --side-records /tmp/ab_side.json > /tmp/ab.json 2>/dev/null
     python3 - $1 $2 >> $out <<'PY'
 import json, sys

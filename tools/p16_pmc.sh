@@ -8,7 +8,7 @@ repo=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$repo/gpurun_out/${tag}_p16_pmc.txt
 mkdir -p $repo/gpurun_out
 : > $out
-run="python3 $repo/bench.py --config transformer --precision bf16x3 --steps 4 --warmup 1 --no-preroll --regions 1 --no-cpu-baseline --no-side --no-api --streams 1 --no-graph --side-records /tmp/side_pmc.json"
+run="python3 $repo/bench.py --full --config transformer --precision bf16x3 --steps 4 --warmup 1 --no-preroll --regions 1 --no-cpu-baseline --no-side --no-api --streams 1 --no-graph --side-records /tmp/side_pmc.json"
 kernel=position_wise16_kernel
 echo "== $kernel: waves and waits" >> $out
 $repo/tools/pmc_kernel.sh $kernel SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY -- $run >> $out 2>&1

@@ -7,8 +7,8 @@ repo=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$repo/gpurun_out/${tag}_pmc_utilisation.txt
 mkdir -p $repo/gpurun_out
 : > $out
-conv="python3 $repo/bench.py --steps 10 --warmup 2 --no-preroll --regions 1 --no-cpu-baseline --no-api --no-side --streams 1"
-tr="python3 $repo/bench.py --config transformer --steps 4 --warmup 1 --no-preroll --regions 1 --no-cpu-baseline --no-side --streams 1"
+conv="python3 $repo/bench.py --full --steps 10 --warmup 2 --no-preroll --regions 1 --no-cpu-baseline --no-api --no-side --streams 1"
+tr="python3 $repo/bench.py --full --config transformer --steps 4 --warmup 1 --no-preroll --regions 1 --no-cpu-baseline --no-side --streams 1"
 echo "== conv1d_stack_kernel: matrix pipe" >> $out
 $repo/tools/pmc_kernel.sh conv1d_stack_kernel SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- $conv >> $out 2>&1
 echo "== conv1d_stack_kernel: waits" >> $out

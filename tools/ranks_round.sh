@@ -7,10 +7,10 @@ repo=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$repo/gpurun_out
 mkdir -p $out
 cd $repo
-python3 bench.py --gpus 2 --backend gloo > $out/${tag}_bench_2ranks_gloo_1gpu.json 2> $out/${tag}_ranks.err
+python3 bench.py --full --gpus 2 --backend gloo > $out/${tag}_bench_2ranks_gloo_1gpu.json 2> $out/${tag}_ranks.err
 for workload in corpus longform; do
-    python3 bench.py --workload $workload --steps 5 --warmup 2 > $out/${tag}_strong_${workload}_1gpu.json 2>> $out/${tag}_ranks.err
-    python3 bench.py --workload $workload --steps 5 --warmup 2 --gpus 2 --backend gloo \
+    python3 bench.py --full --workload $workload --steps 5 --warmup 2 > $out/${tag}_strong_${workload}_1gpu.json 2>> $out/${tag}_ranks.err
+    python3 bench.py --full --workload $workload --steps 5 --warmup 2 --gpus 2 --backend gloo \
         > $out/${tag}_strong_${workload}_2ranks_gloo_1gpu.json 2>> $out/${tag}_ranks.err
 done
 python3 - $out $tag <<'PY'

@@ -7,7 +7,7 @@ repo=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$repo/gpurun_out/${tag}_split_pmc.txt
 mkdir -p $repo/gpurun_out
 : > $out
-run="python3 $repo/bench.py --config transformer --precision bf16x3 --steps 4 --warmup 1 --no-preroll --regions 1 --no-cpu-baseline --no-side --no-api --streams 1 --no-graph --side-records /tmp/side_pmc.json"
+run="python3 $repo/bench.py --full --config transformer --precision bf16x3 --steps 4 --warmup 1 --no-preroll --regions 1 --no-cpu-baseline --no-side --no-api --streams 1 --no-graph --side-records /tmp/side_pmc.json"
 # (position_wise16_kernel: five launches of block + next projections, one of the first
 # layer's projections and one of the last layer's block per step - the mean is over all)
 for kernel in position_wise16_kernel attention_split_kernel; do
@@ -19,7 +19,7 @@ for kernel in position_wise16_kernel attention_split_kernel; do
     $repo/tools/pmc_kernel.sh $kernel SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- $run >> $out 2>&1
 done
 # the frame-rate convs of configs[1] at bf16x3
-run="python3 $repo/bench.py --precision bf16x3 --steps 10 --warmup 2 --no-preroll --regions 1 --no-cpu-baseline --no-side --no-api --streams 1 --no-graph --side-records /tmp/side_pmc.json"
+run="python3 $repo/bench.py --full --precision bf16x3 --steps 10 --warmup 2 --no-preroll --regions 1 --no-cpu-baseline --no-side --no-api --streams 1 --no-graph --side-records /tmp/side_pmc.json"
 kernel=conv1d_split_kernel
 for counter in FETCH_SIZE WRITE_SIZE; do
     echo "== $kernel: $counter (KB units of the counter; FETCH doubles on gfx950 per the guide)" >> $out

@@ -6,7 +6,7 @@ out=$repo/gpurun_out
 mkdir -p $out
 cd $repo
 for precision in bf16x3 bf16x3_fast bf16x6; do
-    python3 bench.py --config transformer --precision $precision --steps 50 --warmup 5 \
+    python3 bench.py --full --config transformer --precision $precision --steps 50 --warmup 5 \
         --no-cpu-baseline --no-side --side-records $out/split_${precision}.json \
         > $out/split_${precision}.line 2>> $out/split_try.err
     python3 - $out/split_${precision}.json <<'PY'
