@@ -26,6 +26,8 @@ from .core import (  # noqa: F401
     inference_context, postprocess, preprocess, resample, segment)
 # the paper's baselines behind Config.method (emphases.baselines.*)
 from . import baselines  # noqa: F401,E402
+# dataset evaluation (emphases.evaluate.{datasets, Metrics, metrics})
+from . import evaluate  # noqa: F401,E402
 # the torch.library operator seams (torch.ops.emphases_amd.*): registration
 # only, nothing runs at import
 from . import ops  # noqa: F401,E402

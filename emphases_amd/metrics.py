@@ -13,6 +13,10 @@ restated here from their published definitions:
     Average             total / count
     MeanStd             mean and the (count - 1)-normalised standard deviation
     PearsonCorrelation  sum((p - mean_p)(t - mean_t)) / count / (std_p std_t)
+
+`grouped` is the per-file form behind `emphases_amd.evaluate`: one row of the
+same sums per group of a compact word axis (`emph_word_metrics_grouped`),
+stored by a fixed-order reduction, so every row is bitwise reproducible.
 """
 import math
 
@@ -21,6 +25,52 @@ import torch
 
 from . import config as cfg
 from . import runtime
+
+
+def forms(method=None, loss=None):
+    """(post, bce_form) of the kernels for the reference's (METHOD, LOSS):
+    `emphases.postprocess` is the identity for any method but 'neural'
+    (`core.py:335-342`), while `BinaryCrossEntropy` follows LOSS alone
+    (`evaluate/metrics.py:59-76`)."""
+    loss = loss or cfg.DEFAULT.loss
+    post = runtime.POSTPROCESS[loss] if method in (None, 'neural') else \
+        runtime.POSTPROCESS[None]
+    return post, runtime.BCE_FORMS[loss]
+
+
+def grouped(logits, targets, cu_words, post, bce_form, predicted_mean=0.,
+            target_mean=0., out=None):
+    """float64 [groups, METRIC_FIELDS] on the device: the sums of the words
+    `cu_words[g] .. cu_words[g + 1] - 1` of `logits` / `targets` (compact
+    float32 [n] device tensors) for every group g, one launch.  `cu_words`:
+    int64 [groups + 1], host or device; checked on the host (non-decreasing,
+    from 0 to n) before it reaches the kernel."""
+    device = logits.device
+    host = torch.as_tensor(cu_words, dtype=torch.int64).cpu().reshape(-1)
+    if host.numel() < 1 or int(host[0]) != 0 or \
+            int(host[-1]) != logits.numel() or \
+            targets.numel() != logits.numel() or \
+            bool((host[1:] < host[:-1]).any()):
+        raise ValueError(
+            'grouped: cu_words must rise from 0 to the number of words '
+            f'({logits.numel()} logits, {targets.numel()} targets)')
+    if logits.dtype != torch.float32 or targets.dtype != torch.float32 or \
+            not logits.is_cuda or targets.device != device:
+        raise ValueError('grouped: float32 logits and targets on one device')
+    groups = host.numel() - 1
+    if groups >= 2 ** 31:
+        raise ValueError(f'grouped: {groups} groups (at most 2^31 - 1)')
+    logits, targets = logits.contiguous(), targets.contiguous()
+    if out is None:
+        out = torch.empty((groups, runtime.METRIC_FIELDS),
+                          dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        cu = host.to(device, non_blocking=False)
+        runtime.check(runtime.library().emph_word_metrics_grouped(
+            logits.data_ptr(), targets.data_ptr(), cu.data_ptr(), groups,
+            post, bce_form, float(predicted_mean), float(target_mean),
+            out.data_ptr(), runtime.stream()), 'emph_word_metrics_grouped')
+    return out
 
 
 def _packed(values, lengths, device):
@@ -41,12 +91,19 @@ def _packed(values, lengths, device):
 
 
 class _Accumulator:
-    """float64 [METRIC_FIELDS] sums on the device."""
+    """float64 [METRIC_FIELDS] sums on the device.  `method`: None or
+    'neural' is `emph_word_metrics` (the BCE form follows the postprocess);
+    a baseline scores its outputs as they are with the LOSS's BCE form, which
+    only `emph_word_metrics_grouped` expresses: each batch's words are then
+    compacted on the device and summed as one group."""
 
-    def __init__(self, gpu=None, loss=None):
+    def __init__(self, gpu=None, loss=None, method=None):
         self.device = runtime.require_gpu(gpu)
         self.lib = runtime.library()
         self.post = runtime.POSTPROCESS[loss or cfg.DEFAULT.loss]
+        self.grouped = None
+        if method not in (None, 'neural'):
+            self.grouped = forms(method, loss)
         self.predicted_mean = 0.
         self.target_mean = 0.
         self.reset()
@@ -59,6 +116,14 @@ class _Accumulator:
         """`logits`, `targets` float32 [n], `mask` int32 [n] (>= 0 = a word),
         all on the device - e.g. an engine's packed `logits` and the plan's
         `word_segment` table, without any gather."""
+        if self.grouped is not None:
+            keep = mask >= 0
+            logits, targets = logits[keep], targets[keep]
+            row = grouped(logits, targets, [0, logits.numel()],
+                          *self.grouped, self.predicted_mean,
+                          self.target_mean)
+            self.sums += row[0]
+            return
         with torch.cuda.device(self.device):
             runtime.check(self.lib.emph_word_metrics(
                 logits.data_ptr(), targets.data_ptr(), mask.data_ptr(),
@@ -71,10 +136,17 @@ class _Accumulator:
 
 
 class Metrics:
-    """`emphases/evaluate/metrics.py:12-51`"""
+    """`emphases/evaluate/metrics.py:12-51`.  `method` (keyword only): the
+    reference's METHOD; None (default) or 'neural' postprocesses the logits
+    (sigmoid / clamp by `loss`), a baseline's scores are taken as they are
+    and BCE is the `loss`'s form (with logits under 'bce')."""
 
-    def __init__(self, predicted_stats, target_stats, gpu=None, loss=None):
-        self._sums = _Accumulator(gpu, loss)
+    def __init__(self, predicted_stats, target_stats, gpu=None, loss=None, *,
+                 method=None):
+        if method is not None and method not in cfg.METHODS:
+            raise ValueError(
+                f'Emphasis annotation method {method} is not defined')
+        self._sums = _Accumulator(gpu, loss, method)
         predicted_mean, self.predicted_std = predicted_stats()
         target_mean, self.target_std = target_stats()
         self._sums.predicted_mean = float(predicted_mean)

@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -29,6 +29,8 @@ ACTIVATIONS = {None: 0, 'none': 0, 'relu': 1, 'gelu': 2, 'silu': 3,
                'leaky_relu': 4}
 REDUCTIONS = {'sum': 0, 'average': 1, 'max': 2, 'center': 3}
 POSTPROCESS = {None: 0, 'bce': 1, 'mse': 2}
+# BCE forms of emph_word_metrics_grouped, by LOSS
+BCE_FORMS = {'bce': 0, 'mse': 1}
 AUDIO_F32, AUDIO_PCM16 = 0, 1
 SPREAD_IDENTITY, SPREAD_LOG2 = 0, 1
 (METRIC_COUNT, METRIC_BCE, METRIC_SQUARED_ERROR, METRIC_COVARIANCE,
@@ -181,6 +183,8 @@ SIGNATURES = {
         _ptr, _i64, _ptr, _i32, _i32, _i32, _ptr, _i32, _f32, _ptr, _i32, _ptr]),
     'emph_word_metrics': (_c.c_int, [
         _ptr, _ptr, _ptr, _i64, _i32, _f32, _f32, _ptr, _ptr]),
+    'emph_word_metrics_grouped': (_c.c_int, [
+        _ptr, _ptr, _ptr, _i32, _i32, _i32, _f32, _f32, _ptr, _ptr]),
     'emph_add_layernorm': (_c.c_int, [
         _ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _f32, _i64, _i64, _ptr]),
     'emph_quantile_spreads': (_c.c_int, [

@@ -272,6 +272,7 @@ class _Layout:
         self.meta = None
         self.replay = None
         self.scores = None
+        self.logits = None
         self.seen = 0
 
 
@@ -320,9 +321,11 @@ class Scores:
 
 class Pending:
     """Scores of a submitted batch; `result()` waits for them (a list of
-    per-utterance tensors), `scores()` for the same as a `Scores`."""
+    per-utterance tensors), `scores()` for the same as a `Scores`.  A batch
+    submitted with `logits=True` also keeps the decoder's logits:
+    `logits()` is their `Scores`, gathered the way the scores are."""
 
-    def __init__(self, lane, plan, count, on_device, ld_words):
+    def __init__(self, lane, plan, count, on_device, ld_words, logits=False):
         self._lane = lane
         self._plan = plan
         self._count = count
@@ -331,11 +334,22 @@ class Pending:
         self._scores = None
         self._value = None
         self._dense = None
+        self._want_logits = logits
+        self._logits = None
+        self._logits_dense = None
 
     def result(self):
         if self._value is None:
             self._value = list(self.scores())
         return self._value
+
+    def logits(self):
+        """The logits of the batch as a `Scores` (same layout, device and
+        dtype as `scores()`); only for a batch submitted with `logits=True`."""
+        if not self._want_logits:
+            raise RuntimeError('submit the batch with logits=True')
+        self.scores()
+        return self._logits_dense
 
     def scores(self):
         if self._dense is not None:
@@ -346,6 +360,9 @@ class Pending:
             if self._on_device:
                 empty = empty.to(lane.device)
             self._dense = Scores(empty, np.zeros(self._count, dtype=np.int64))
+            if self._want_logits:
+                self._logits_dense = Scores(
+                    empty.clone(), np.zeros(self._count, dtype=np.int64))
             return self._dense
         with lane.lock:
             if self._dense is not None:
@@ -366,6 +383,16 @@ class Pending:
                 dense = torch.from_numpy(
                     lane.result[:self._ld_words].numpy()[
                         plan.word_columns()])[None]
+            logits = None
+            if self._logits is not None:
+                # (kept on the device whatever `on_device`: the same gather
+                # there, then the host copy if the scores are on the host)
+                packed = self._logits
+                packed.record_stream(torch.cuda.current_stream(lane.device))
+                columns = torch.from_numpy(plan.word_columns())
+                logits = packed[columns.to(packed.device)][None]
+                if not self._on_device:
+                    logits = logits.cpu()
             if lane.pending is self:
                 lane.pending = None
         # one gather of the valid word columns, one split: per-utterance views
@@ -373,7 +400,10 @@ class Pending:
         counts = np.bincount(
             plan.utterance, weights=plan.words, minlength=self._count)
         self._dense = Scores(dense, counts.astype(np.int64))
+        if logits is not None:
+            self._logits_dense = Scores(logits, counts.astype(np.int64))
         self._scores = None
+        self._logits = None
         return self._dense
 
 
@@ -473,13 +503,15 @@ class Session:
 
     def submit(self, alignments, audios, sample_rate=cfg.SAMPLE_RATE,
                batch_size=None, on_device=False, pitch_tracker=None,
-               plan=None):
+               plan=None, *, logits=False):
         """Enqueue a batch; returns a `Pending`.  The lane it takes is the one
         whose batch was submitted `depth` submissions ago: that batch's
         results are extracted first if the caller has not done so.  `plan`:
         the batch's plan when the caller has it already (`batch.plan_batch` of
         the same alignments and 16 kHz lengths, maybe `Engine.prepare`d on
-        another thread): no layout cache lookup, no planning here."""
+        another thread): no layout cache lookup, no planning here.
+        `logits`: also keep the decoder's logits (`Pending.logits()`; one
+        device copy of the packed word axis, made only when asked for)."""
         with self._lock:
             lane = self.lanes[self._cursor % len(self.lanes)]
             self._cursor += 1
@@ -489,7 +521,8 @@ class Session:
                 try:
                     return self._enqueue(
                         lane, list(alignments), list(audios), sample_rate,
-                        batch_size, on_device, pitch_tracker, plan)
+                        batch_size, on_device, pitch_tracker, plan,
+                        logits=logits)
                 except BaseException:
                     # Copies and kernels may already be queued on the lane's
                     # stream with no `done` event behind them: drain it before
@@ -567,7 +600,7 @@ class Session:
         return pending
 
     def _enqueue(self, lane, alignments, audios, sample_rate, batch_size,
-                 on_device, pitch_tracker, ready=None):
+                 on_device, pitch_tracker, ready=None, logits=False):
         audios = [mono(audio) for audio in audios]
         resampling = int(sample_rate) != cfg.SAMPLE_RATE
         pcm = bool(audios) and all(
@@ -606,7 +639,7 @@ class Session:
         plan = layout.plan if layout is not None else None
         pending = Pending(
             lane, plan, len(audios), on_device,
-            plan.ld_words if plan is not None else 0)
+            plan.ld_words if plan is not None else 0, logits)
         if plan is None or not len(plan):
             return pending
         engine = lane.engine
@@ -653,13 +686,16 @@ class Session:
                     engine.sub_plans(plan) is None:
                 # the layout came back: from now on one graph launch
                 layout.meta = engine.upload(plan)
-                layout.replay, layout.scores, _ = engine.capture(
-                    packed, plan, layout.meta)
+                layout.replay, layout.scores, layout.logits = \
+                    engine.capture(packed, plan, layout.meta)
             if tracks is None and layout.replay is not None:
                 layout.replay()
-                scores = layout.scores
+                scores, word_logits = layout.scores, layout.logits
             else:
-                scores, _ = engine.forward(packed, plan, tracks=tracks)
+                scores, word_logits = engine.forward(
+                    packed, plan, tracks=tracks)
+            if logits:
+                pending._logits = word_logits.clone()
             if on_device:
                 pending._scores = scores.clone()
             else:
@@ -670,16 +706,21 @@ class Session:
         return pending
 
     def run(self, alignments, audios, sample_rate=cfg.SAMPLE_RATE,
-            batch_size=None, on_device=False, pitch_tracker=None):
+            batch_size=None, on_device=False, pitch_tracker=None, *,
+            logits=False):
         """submit + result: one synchronous batch (very large ones as a few
         sub-batches in flight, see SPLIT_BYTES; an utterance's scores do not
-        depend on its neighbours in a batch)."""
+        depend on its neighbours in a batch).  `logits`: return
+        `(scores, logits)`, two lists of per-utterance [1, W_u] tensors."""
         alignments, audios = list(alignments), list(audios)
         groups = self._groups(audios)
         pendings = [
             self.submit(alignments[lo:hi], audios[lo:hi], sample_rate,
-                        batch_size, on_device, pitch_tracker)
+                        batch_size, on_device, pitch_tracker, logits=logits)
             for lo, hi in groups]
+        if logits:
+            return ([s for pending in pendings for s in pending.result()],
+                    [x for pending in pendings for x in pending.logits()])
         if len(pendings) == 1:
             return pendings[0].result()
         return [scores for pending in pendings for scores in pending.result()]

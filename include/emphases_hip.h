@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 31
+#define EMPH_ABI_VERSION 32
 
 /* Segment-table fields */
 enum {
@@ -872,6 +872,40 @@ int emph_word_metrics(const float* logits, const float* targets,
                       const int32_t* word_segment, int64_t total, int32_t post,
                       float predicted_mean, float target_mean,
                       double* accumulators, void* stream);
+
+/* BCE forms of emph_word_metrics_grouped (evaluate/metrics.py:59-76) */
+enum {
+    EMPH_BCE_WITH_LOGITS = 0,   /* binary_cross_entropy_with_logits (LOSS 'bce') */
+    EMPH_BCE_CLAMPED_LOG = 1    /* -(y log(c + 1e-6) + (1 - y) log(1 - c + 1e-6)),
+                                   c = clamp(x, 0, 1) (LOSS 'mse')              */
+};
+
+/* out[g][EMPH_METRIC_*] = the sums of emph_word_metrics over the words of
+ * group g alone, for every group of a compact word axis in one launch: the
+ * per-file ("granular") rows of emphases/evaluate/core.py:15-127.
+ *
+ *   logits, targets  float32 [cu_words[groups]]  compact words, groups back to
+ *                                     back (no padding columns)
+ *   cu_words         int64 [groups + 1]  group g owns words cu_words[g] ..
+ *                                     cu_words[g + 1] - 1 (non-decreasing; an
+ *                                     empty group gets a row of zeros)
+ *   post             EMPH_POST_*      the score transform (emphases.postprocess:
+ *                                     NONE for any METHOD other than 'neural')
+ *   bce_form         EMPH_BCE_*       the BCE form (the LOSS switch), chosen
+ *                                     independently of `post`
+ *   predicted_mean, target_mean       as for emph_word_metrics
+ *   out              float64 [groups][EMPH_METRIC_FIELDS], STORED (no atomics,
+ *                                     no zeroing needed)
+ *
+ * Bitwise reproducible: a row depends only on its group's words (a fixed-order
+ * reduction per group), not on the group's position, the other groups or the
+ * launch.
+ */
+int emph_word_metrics_grouped(const float* logits, const float* targets,
+                              const int64_t* cu_words, int32_t groups,
+                              int32_t post, int32_t bce_form,
+                              float predicted_mean, float target_mean,
+                              double* out, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Baselines                                                                 */
