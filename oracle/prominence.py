@@ -8,6 +8,7 @@ What it restates (paths relative to /root/reference):
   chunks()            emphases/core.py:345-418 (`preprocess`), convert.py:9-36
   logmel()            emphases/data/preprocess/mels.py:16-59,94-109
   loudness()          emphases/data/preprocess/loudness.py:59-120
+  peak_power()        the maximum `top_db` hangs on (librosa.amplitude_to_db)
   downsample()        emphases/core.py:426-469
   segment()           emphases/core.py:552-586
   conv_stack()        emphases/model/layers/convolution.py:13-37
@@ -23,6 +24,10 @@ so parity is defined against its own modules in fp32.
 The model half (`forward`, `stack`, `conv_stack`, `transformer_stack`) runs in
 the dtype of its inputs: given float64 features and weights it is the float64
 reference the device paths are measured against (tests/test_gpu_paths.py).
+The feature half (`logmel`, `loudness`, `features`, `peak_power`) follows the
+dtype of the audio in the same way: float64 audio gets float64 arithmetic on
+the model's float32 constants (Hann windows, mel basis, A-weights), upcast
+exactly - the reference of the device front-end (tests/test_gpu_frontend.py).
 
 Pinning: first-party behaviour is pinned by `tests/golden/*.npz`, captured by
 importing the unmodified reference (`tests/golden/generate.py`).  Third-party
@@ -117,27 +122,58 @@ def mel_basis():
     return _BASIS
 
 
-def logmel(audio, normalize=False):
-    """mels.py:16-59: audio float32 [1, S] -> [80, F]."""
+def hann_window(dtype=torch.float32):
+    """mels.py:39-41: the periodic Hann as torch evaluates it in float32.  A
+    float64 caller gets those float32 values, exactly: the window is a constant
+    of the model like the mel basis (see `positional_encoding`)."""
+    return torch.hann_window(WINDOW_SIZE, dtype=torch.float32).to(dtype)
+
+
+def reflect_pad(audio):
+    """mels.py:31-36 / loudness.py:70-75: [1, S] -> [S + 864]."""
     size = (NUM_FFT - HOPSIZE) // 2
-    audio = torch.nn.functional.pad(
-        audio[None], (size, size), mode='reflect')[0]          # mels.py:31-36
-    window = torch.hann_window(WINDOW_SIZE, dtype=audio.dtype)
+    return torch.nn.functional.pad(
+        audio[None], (size, size), mode='reflect')[0, 0]
+
+
+def magnitude(padded):
+    """mels.py:39-51: reflect-padded audio [S + 864] -> sqrt(|X|^2 + 1e-6)
+    [513, F] in the dtype of the audio."""
     stft = torch.stft(
-        audio, NUM_FFT, hop_length=HOPSIZE, window=window, center=False,
-        normalized=False, onesided=True, return_complex=True)
+        padded[None], NUM_FFT, hop_length=HOPSIZE,
+        window=hann_window(padded.dtype), center=False, normalized=False,
+        onesided=True, return_complex=True)
     stft = torch.view_as_real(stft)[0]                         # mels.py:48
-    spectrogram = torch.sqrt(stft.pow(2).sum(-1) + 1e-6)       # mels.py:51
-    mels = torch.log(torch.clamp(
-        torch.matmul(mel_basis(), spectrogram), min=1e-5))     # mels.py:106-109
+    return torch.sqrt(stft.pow(2).sum(-1) + 1e-6)              # mels.py:51
+
+
+def mel(audio, basis=None):
+    """The mel rows before the clamp and the log: [1, S] -> [80, F].  The
+    float32 basis, upcast exactly when the audio is float64."""
+    basis = mel_basis() if basis is None else basis
+    return torch.matmul(
+        basis.to(audio.dtype), magnitude(reflect_pad(audio)))  # mels.py:106
+
+
+def log_of_mel(mels, normalize=False):
+    mels = torch.log(torch.clamp(mels, min=1e-5))              # mels.py:107-109
     if normalize:
         return (mels + 10.) / 10.                              # mels.py:57-58
     return mels
 
 
-def a_weights():
-    """loudness.py:110-120 — A-weighting evaluated on penn's 8 kHz / 1024 grid
-    (a quirk of the reference), minus REF_DB=20."""
+def logmel(audio, normalize=False):
+    """mels.py:16-59: audio [1, S] -> [80, F], in the dtype of the audio:
+    float32 restates the reference; float64 is the same algorithm in float64
+    on the float32 window and mel basis, the high-precision reference of the
+    device front-end (tests/test_gpu_frontend.py)."""
+    return log_of_mel(mel(audio), normalize)
+
+
+def a_weights(dtype=np.float64):
+    """loudness.py:110-120 - A-weighting evaluated on penn's 8 kHz / 1024 grid
+    (a quirk of the reference), minus REF_DB=20.  `dtype=np.float32`: rounded
+    as the engine uploads them."""
     frequencies = np.fft.rfftfreq(n=1024, d=1.0 / 8000)
     f_sq = frequencies ** 2.0
     const = np.array([12194.217, 20.598997, 107.65265, 737.86223]) ** 2.0
@@ -147,30 +183,63 @@ def a_weights():
             - np.log10(f_sq + const[0]) - np.log10(f_sq + const[1])
             - 0.5 * np.log10(f_sq + const[2])
             - 0.5 * np.log10(f_sq + const[3]))
-    return np.maximum(-80.0, weights)[:, None] - 20.
+    return (np.maximum(-80.0, weights)[:, None] - 20.).astype(dtype)
 
 
-def loudness(audio, normalize=False):
-    """loudness.py:59-107: audio float32 [1, S] -> [1, F] (numpy on CPU)."""
-    p = (NUM_FFT - HOPSIZE) // 2
-    padded = torch.nn.functional.pad(
-        audio[:, None], (p, p), 'reflect').squeeze(1)[0].numpy()
+def loudness_window():
+    """The periodic Hann of the loudness row: evaluated in float64 and rounded
+    to float32 (up to 3 float32 ulp from `hann_window`, which torch evaluates
+    in float32; the device's one table is this one)."""
     n = np.arange(WINDOW_SIZE)
-    window = (0.5 - 0.5 * np.cos(
+    return (0.5 - 0.5 * np.cos(
         2.0 * np.pi * n / WINDOW_SIZE)).astype(np.float32)
+
+
+def power(audio):
+    """loudness.py:59-83: audio [1, S] -> |X|^2 [513, F] (numpy), in the dtype
+    of the audio.  Float32 goes through librosa's complex64 spectrogram;
+    float64 keeps the float32-rounded window and nothing else of float32."""
+    padded = reflect_pad(audio).numpy()
+    window = loudness_window()
     frames = 1 + (len(padded) - WINDOW_SIZE) // HOPSIZE
     index = np.arange(WINDOW_SIZE)[:, None] + HOPSIZE * np.arange(frames)[None]
-    stft = np.fft.rfft(
-        window[:, None] * padded[index], axis=0).astype(np.complex64)
+    stft = np.fft.rfft(window[:, None] * padded[index], axis=0)
+    if padded.dtype == np.float32:
+        stft = stft.astype(np.complex64)
     magnitude = np.abs(stft)
-    db = 10.0 * np.log10(np.maximum(1e-10, magnitude * magnitude))
-    db = np.maximum(db, db.max() - 80.0)       # top_db over the whole chunk
-    weighted = db + a_weights()
+    return magnitude * magnitude
+
+
+def peak_power(audio):
+    """max |X|^2 over a chunk's frames and 513 bins: what `top_db` hangs the
+    chunk's floor on (`emph_frontend_peak` computes it per segment)."""
+    return power(audio).max()
+
+
+def loudness_of_power(power, normalize=False, peak=None):
+    """loudness.py:84-107 on |X|^2 [513, F] -> [1, F].  `peak`: the power the
+    `top_db` floor hangs on, when it is not the chunk's own."""
+    db = 10.0 * np.log10(np.maximum(1e-10, power))
+    top = db.max() if peak is None else \
+        10.0 * np.log10(np.maximum(1e-10, power.dtype.type(peak)))
+    db = np.maximum(db, top - 80.0)            # top_db over the whole chunk
+    single = power.dtype == np.float32
+    weighted = db + (a_weights() if single else
+                     a_weights(np.float32).astype(np.float64))
     weighted[weighted < -100.] = -100.                     # loudness.py:97
-    result = torch.from_numpy(weighted.mean(axis=0)).float()[None]
+    result = torch.from_numpy(weighted.mean(axis=0))
+    result = (result.float() if single else result)[None]
     if normalize:
         return (result + 100.) / 100.
     return result
+
+
+def loudness(audio, normalize=False):
+    """loudness.py:59-107: audio [1, S] -> [1, F] (numpy on CPU), in the dtype
+    of the audio: float32 restates the reference; float64 is the same
+    algorithm in float64 on the float32 window and the float32 A-weights the
+    engine uploads."""
+    return loudness_of_power(power(audio), normalize)
 
 
 def features(audio, cfg, pitch_tracker=None):
@@ -178,7 +247,8 @@ def features(audio, cfg, pitch_tracker=None):
     periodicity come from `penn` (a neural tracker, not restatable):
     `pitch_tracker(audio [1, S]) -> (pitch [1, F] Hz, periodicity [1, F])`
     stands in for `penn.from_audio` (core.py:84-92); what the reference does
-    with its outputs (core.py:94-106) is restated here."""
+    with its outputs (core.py:94-106) is restated here.  The mel and loudness
+    rows follow the dtype of `audio`, and so does the result."""
     rows = []
     if cfg.get('mel_feature', True):
         rows.append(logmel(audio, cfg.get('normalize', False)))
@@ -198,6 +268,8 @@ def features(audio, cfg, pitch_tracker=None):
             rows.append(periodicity)
     if cfg.get('loudness_feature'):
         rows.append(loudness(audio, cfg.get('normalize', False)))
+    # (the tracker's float32 rows ride along exactly in a float64 matrix)
+    rows = [row.to(audio.dtype) for row in rows]
     return (rows[0] if len(rows) == 1 else torch.cat(rows))[None]
 
 

@@ -384,3 +384,292 @@ def test_float64_oracle_matches_variant_goldens(variants):
         assert np.abs(logits.numpy() - want).max() < 1e-5 * scale, name
         checked += 1
     assert checked == 39
+
+
+###############################################################################
+# the float64 front-end (the reference of tests/test_gpu_frontend.py)
+###############################################################################
+
+
+def test_float64_frontend_matches_float32_on_seams(seams):
+    """`logmel` / `loudness` / `features` follow the dtype of the audio; the
+    float64 evaluation is the float32 one up to float32's own rounding."""
+    for name in seams['audio/names']:
+        audio = torch.from_numpy(seams[f'audio/{name}'])
+        for normalize in (False, True):
+            single = oracle.logmel(audio, normalize)
+            double = oracle.logmel(audio.double(), normalize)
+            assert single.dtype == torch.float32
+            assert double.dtype == torch.float64
+            assert float((single - double).abs().max()) < 1e-5
+            single = oracle.loudness(audio, normalize)
+            double = oracle.loudness(audio.double(), normalize)
+            assert single.dtype == torch.float32
+            assert double.dtype == torch.float64 and double.shape == single.shape
+            assert float((single - double).abs().max()) < \
+                (2e-7 if normalize else 2e-5)
+        overrides = {'loudness_feature': True, 'pitch_feature': True}
+        both = oracle.features(audio.double(), overrides, synth.pitch_tracks)
+        assert both.dtype == torch.float64 and both.shape[1] == 82
+        assert torch.equal(both[0, :80], oracle.logmel(audio.double()))
+        assert torch.equal(both[0, 81:], oracle.loudness(audio.double()))
+        single = oracle.features(audio, overrides, synth.pitch_tracks)
+        assert single.dtype == torch.float32
+        assert torch.equal(both[0, 80], single[0, 80].double())
+        peak = oracle.peak_power(audio.double())
+        assert peak == oracle.power(audio.double()).max()
+        assert abs(float(oracle.peak_power(audio)) - peak) < 1e-6 * peak
+
+
+def test_float64_frontend_uses_the_float32_constants():
+    """Float64 arithmetic on the model's own float32 constants: the window
+    torch builds in float32, the float32 mel basis, the A-weights as the engine
+    uploads them."""
+    from emphases_amd import engine, melbasis
+    assert torch.equal(oracle.hann_window(torch.float64),
+                       torch.hann_window(1024).double())
+    assert np.array_equal(melbasis.default().dense, oracle.mel_basis().numpy())
+    assert np.array_equal(
+        engine.a_weighting(), oracle.a_weights(np.float32)[:, 0])
+    # the device has ONE window table (halved: the 1/2 of the real-FFT split):
+    # the loudness row's, the Hann evaluated in float64 and rounded once.  The
+    # mel rows' window, evaluated by torch in float32, is up to 3 ulp from it
+    # - which alone is up to 5e-6 on the metric of tests/frontend_signals.py
+    # (the step), inside the device's budget there
+    from emphases_amd import runtime
+    table = 2. * np.asarray(runtime.frontend_table())[:1024]
+    assert np.array_equal(table, oracle.loudness_window())
+    gap = np.abs(table - oracle.hann_window().numpy())
+    assert gap.max() <= 3 * 2. ** -24
+
+
+def direct_dft(frame, bins):
+    """sum_n frame[n] exp(-2 pi i k n / 1024) for k in bins: no FFT."""
+    n = np.arange(1024)
+    return np.array([
+        np.sum(frame * np.exp(-2j * np.pi * ((k * n) % 1024) / 1024.))
+        for k in bins])
+
+
+def test_float64_frontend_closed_forms():
+    """Answers that need no FFT, in float64, to 1e-12 (relative)."""
+    basis = oracle.mel_basis().double()
+    rowsum = basis.sum(dim=1)
+    window = oracle.hann_window(torch.float64).numpy()
+    weights_ = oracle.a_weights(np.float32).astype(np.float64)[:, 0]
+    close = lambda got, want: np.testing.assert_allclose(   # noqa: E731
+        np.asarray(got), np.asarray(want), rtol=1e-12, atol=0)
+
+    # silence: every magnitude is sqrt(1e-6); every power clamps to 1e-10
+    silence = torch.zeros(1, 4000, dtype=torch.float64)
+    mel = oracle.logmel(silence)
+    assert mel.shape == (80, 25)
+    close(mel, torch.log(rowsum * 1e-3)[:, None].expand(80, 25))
+    assert float(rowsum.min()) * 1e-3 > 6e-5          # the 1e-5 clamp is dead
+    assert torch.equal(
+        oracle.loudness(silence), torch.full((1, 25), -100., dtype=torch.float64))
+    assert torch.equal(
+        oracle.loudness(silence, True), torch.zeros(1, 25, dtype=torch.float64))
+    assert oracle.peak_power(silence) == 0.
+
+    # DC: X[k] = c sum_n w[n] exp(-2 pi i k n / 1024), the window's own sums
+    for level in (32767. / 32768., -1., 1. / 32768.):
+        dc = torch.full((1, 4000), level, dtype=torch.float64)
+        want = np.abs(level * direct_dft(window, (0, 1)))
+        close(want[0], abs(level) * window.sum())
+        magnitude = oracle.magnitude(oracle.reflect_pad(dc))
+        close(magnitude[:2, 7], np.sqrt(want ** 2 + 1e-6))
+        # (the loudness row has a window of its own rounding)
+        want = np.abs(level * direct_dft(
+            oracle.loudness_window().astype(np.float64), (0, 1)))
+        power = oracle.power(dc)
+        close(power[:2, 7], want ** 2)
+        close(oracle.peak_power(dc), want[0] ** 2)
+        # bins 0 and 1 carry no mel weight but all of the loudness row: the rest
+        # of the spectrum (the float32 window's rounding, 1e-14) sits on the
+        # floor 80 dB under bin 0
+        top = 10. * np.log10(max(1e-10, want[0] ** 2))
+        db = np.full(513, top - 80.)
+        db[:2] = np.maximum(10. * np.log10(np.maximum(1e-10, want ** 2)), top - 80.)
+        close(oracle.loudness(dc)[0, 7], np.maximum(db + weights_, -100.).mean())
+
+    # an impulse at the centre of frame 5's window: |X[k]| = w[512] = 1 flat
+    impulse = torch.zeros(1, 4000, dtype=torch.float64)
+    impulse[0, 80 + 160 * 5] = 1.
+    assert window[512] == 1.
+    magnitude = oracle.magnitude(oracle.reflect_pad(impulse))
+    close(magnitude[:, 5], np.full(513, math.sqrt(1. + 1e-6)))
+    close(oracle.mel(impulse)[:, 5], rowsum * math.sqrt(1. + 1e-6))
+    np.testing.assert_allclose(oracle.power(impulse)[:, 5], 1., rtol=1e-12)
+    # ... the chunk's peak, so the frame's row is the mean of the A-weights
+    np.testing.assert_allclose(oracle.peak_power(impulse), 1., rtol=1e-12)
+    np.testing.assert_allclose(
+        oracle.loudness(impulse)[0, 5], weights_.mean(), rtol=0, atol=1e-11)
+    # two frames on, the impulse sits at n = 192 of the window
+    close(magnitude[:, 7], np.full(513, math.sqrt(window[192] ** 2 + 1e-6)))
+
+
+###############################################################################
+# does the front-end's budget tell a wrong kernel from a right one?
+###############################################################################
+
+MARGIN = 4.     # tests/test_gpu_frontend.py holds the device to MARGIN x floor
+
+
+def mutated_mel(audio, basis=None, spectrum=None, repeat_edge=False):
+    """`oracle.mel` in float64 with one fault planted."""
+    if repeat_edge:
+        x = audio[0]
+        padded = torch.cat([x[:432].flip(0), x, x[-432:].flip(0)])
+    else:
+        padded = oracle.reflect_pad(audio)
+    magnitude = oracle.magnitude(padded)
+    if spectrum is not None:
+        magnitude = spectrum(magnitude.clone())
+    basis = oracle.mel_basis() if basis is None else basis
+    return basis.double() @ magnitude
+
+
+def basis_without(row, which):
+    """The mel basis with one non-zero of `row` dropped: its first, or the
+    middle one of its run."""
+    basis = oracle.mel_basis().clone()
+    bins = torch.nonzero(basis[row])[:, 0]
+    basis[row, bins[0] if which == 'edge' else bins[len(bins) // 2]] = 0.
+    return basis
+
+
+def swap(target, source):
+    def apply(magnitude):
+        magnitude[target] = magnitude[source]
+        return magnitude
+    return apply
+
+
+def halve(bin_):
+    def apply(magnitude):
+        magnitude[bin_] *= 0.5
+        return magnitude
+    return apply
+
+
+def ripple(magnitude):
+    """Every bin's magnitude off by a relative 2e-5: twiddle or window tables
+    built in reduced precision look like this."""
+    k = torch.arange(513, dtype=torch.float64)
+    return magnitude * (1. + 2e-5 * torch.sin(1.7 * k))[:, None]
+
+
+MEL_MUTATIONS = {
+    'a weight dropped at a run\'s edge': dict(basis=('edge', 40)),
+    'a weight dropped inside a run, row 70': dict(basis=('middle', 70)),
+    'the basis shifted by one bin': dict(basis='shift'),
+    'bin 256 halved': dict(spectrum=halve(256)),
+    'bin 100 takes bin 101\'s value': dict(spectrum=swap(100, 101)),
+    'reflect padding repeats the edge sample': dict(repeat_edge=True),
+    'every bin off by a relative 2e-5': dict(spectrum=ripple)}
+
+
+def test_mel_budget_discriminates():
+    """Every planted fault is over MARGIN x floor on the metric of
+    tests/frontend_signals.py on at least one signal - and the subtle one
+    (2e-5 on every bin) moves `synth.audio(61)`'s log-mel by less than the 2e-5
+    the log-domain tests allow."""
+    import frontend_signals
+    floors = frontend_signals.floors()
+    floor = max(floors['mel', False], floors['mel', True])
+    print(f'\nfloor: {floors["mel", False]:.2e} raw, '
+          f'{floors["mel", True]:.2e} normalised; budget {MARGIN * floor:.2e}')
+    # (what float32 arithmetic needs: 1e-6 raw; the normalised output's own
+    # float32 rounding of (x + 10) / 10 is ten times that in the log)
+    assert 5e-7 < floors['mel', False] < 5e-6 < floors['mel', True] < 3e-5
+    signals = {name: frontend_signals.as_double(pcm)
+               for name, pcm in frontend_signals.signals().items()}
+    clean = {name: oracle.mel(audio) for name, audio in signals.items()}
+    scale = {name: frontend_signals.mel_scale(audio)
+             for name, audio in signals.items()}
+    for title, mutation in MEL_MUTATIONS.items():
+        mutation = dict(mutation)
+        basis = mutation.pop('basis', None)
+        if basis == 'shift':
+            mutation['basis'] = torch.roll(oracle.mel_basis(), 1, dims=1)
+        elif basis is not None:
+            mutation['basis'] = basis_without(basis[1], basis[0])
+        worst = {name: float(((mutated_mel(audio, **mutation) - clean[name])
+                              .abs() / scale[name]).max())
+                 for name, audio in signals.items()}
+        name = max(worst, key=worst.get)
+        print(f'{title}: {worst[name]:.2e} on {name} = '
+              f'{worst[name] / (MARGIN * floor):.1f} x budget')
+        assert worst[name] > MARGIN * floor, title
+        if mutation.get('spectrum') is ripple:
+            log = float((torch.log(mutated_mel(signals['synth61'], **mutation)) -
+                         torch.log(clean['synth61'])).abs().max())
+            print(f'    ... and {log:.2e} in synth61\'s log-mel')
+            assert log < 2e-5
+        elif basis is not None and basis != 'shift':
+            # a misplaced weight shows where its bin leads the frame: the chirp
+            assert worst['chirp'] > MARGIN * floor, title
+
+
+def test_loudness_budget_discriminates():
+    """The two faults the loudness row alone can show - bin 512 read from bin
+    0, and a chunk's `top_db` floor hung on its neighbour's peak - against
+    MARGIN x the float32 oracle's own gap, on the chunks of the multi-chunk
+    batch of tests/test_gpu_frontend.py; and what chunk order that takes."""
+    import frontend_signals
+    floors = frontend_signals.floors()
+    budget = MARGIN * max(floors['db', False], floors['db', True])
+    print(f'\nfloor: {floors["db", False]:.2e} dB raw, '
+          f'{floors["db", True]:.2e} dB normalised; budget {budget:.2e} dB')
+    assert 1e-6 < budget < 1e-4
+    chunks = frontend_signals.batch_chunks(cycles=1)
+    powers = [oracle.power(frontend_signals.as_double(pcm))
+              for _, pcm in chunks]
+    peaks = [power.max() for power in powers]
+    rows = [oracle.loudness_of_power(power) for power in powers]
+
+    def moved(index, peak):
+        return float((oracle.loudness_of_power(powers[index], peak=peak) -
+                      rows[index]).abs().max())
+    for index, (kind, _) in enumerate(chunks):
+        for other in (index - 1, index + 1):
+            if not 0 <= other < len(chunks):
+                continue
+            gap = moved(index, peaks[other])
+            print(f'{kind} with the peak of {chunks[other][0]}: {gap:.1f} dB')
+            assert gap > 1e4 * budget, (kind, chunks[other][0])
+    # ... which is why no two quiet chunks are neighbours there: noise beside
+    # silence hides a leak entirely
+    quiet = [kind for kind, _ in chunks]
+    noise, silence = quiet.index('lsb'), quiet.index('silence')
+    assert moved(noise, peaks[silence]) == 0.
+    assert moved(silence, peaks[noise]) == 0.
+    # ... and why the short loud chunks are DC: three frames of a tone, all
+    # reflections, have hardly a bin 80 dB under their peak for a lower floor
+    # to free (0.0 to 0.1 dB with the tone's phase, against DC's 60)
+    short = oracle.power(frontend_signals.as_double(
+        frontend_signals.signals()['tone_between'][:481]))
+    assert float((oracle.loudness_of_power(short, peak=peaks[noise]) -
+                  oracle.loudness_of_power(short)).abs().max()) < 0.2
+    # bin 512 taking bin 0's value: on the tones and the noise; silence has
+    # nothing to show it with
+    for (kind, _), power, row in zip(chunks, powers, rows):
+        wrong = power.copy()
+        wrong[512] = wrong[0]
+        gap = float((oracle.loudness_of_power(wrong) - row).abs().max())
+        print(f'{kind}, bin 512 <- bin 0: {gap:.2e} dB')
+        assert (gap == 0.) if kind == 'silence' else gap > 10 * budget, kind
+    blind = set()
+    for name, pcm in frontend_signals.signals().items():
+        power = oracle.power(frontend_signals.as_double(pcm))
+        wrong = power.copy()
+        wrong[512] = wrong[0]
+        gap = float((oracle.loudness_of_power(wrong) -
+                     oracle.loudness_of_power(power)).abs().max())
+        print(f'{name}, bin 512 <- bin 0: {gap:.2e} dB')
+        if gap <= 10 * budget:
+            blind.add(name)
+    # (flat spectra, and the tone on bin 256, as far from bin 0 as from bin
+    # 512: both sit on the floor 80 dB under it)
+    assert blind == {'silence', 'impulse', 'tone_bin256'}
