@@ -1,5 +1,6 @@
 """`emphases.data` of the reference, as far as the inference hot path reaches:
 `emphases.data.preprocess` (`/root/reference/emphases/data/__init__.py`).
-Datasets, loaders, samplers and downloads belong to training and are out of
+The feature cache of whole datasets is written by `preprocess.datasets`;
+loaders, samplers, partitions and downloads belong to training and are out of
 scope."""
 from . import preprocess  # noqa: F401

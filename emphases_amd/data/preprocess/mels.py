@@ -18,3 +18,21 @@ def from_audio(audio):
         periodicity_feature=False, loudness_feature=False)
     result, _ = preprocess.features(audio, None, config)
     return result if audio.is_cuda else result.cpu()
+
+
+def from_file(audio_file):
+    """Load audio and compute its log-mel spectrogram [80, F] (`mels.py` `from_file`)."""
+    from ... import load
+    return from_audio(load.audio(audio_file))
+
+
+def from_file_to_file(audio_file, output_file):
+    """`from_file`, saved to `output_file` (its directory is created)."""
+    from_files_to_files([audio_file], [output_file])
+
+
+def from_files_to_files(audio_files, output_files, gpu=None):
+    """The log-mel spectrogram [80, F] of many files, saved to disk: the batched path
+    (`data.preprocess.from_files_to_files`)."""
+    preprocess.from_files_to_files(
+        audio_files, mel_files=list(output_files), gpu=gpu)

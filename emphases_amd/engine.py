@@ -69,6 +69,14 @@ KERNEL_COLUMNS = 1 << 28
 HEAD_DIMS = (32, 40, 64)
 
 
+# (what `Engine.features` and `data.preprocess.datasets` say without a tracker)
+TRACKS_NEEDED = (
+    'pitch/periodicity features come from the third-party '
+    '`penn` tracker; pass its outputs as tracks '
+    '[2, ld_frames] (see core.from_alignments_and_audios '
+    'pitch_tracker=)')
+
+
 def check_supported(config):
     """Raise ValueError for a configuration the kernels cannot run, before
     anything is allocated or launched: the limits the EMPH_REQUIRE checks of
@@ -721,7 +729,7 @@ class Engine:
                 runtime.stream()), 'emph_conv1d')
         return False
 
-    def features(self, audio, plan, meta, tracks=None, config=None):
+    def features(self, audio, plan, meta, tracks=None, config=None, out=None):
         """Feature matrix [num_features, ld_frames] of every segment
         (`data/preprocess/core.py:71-125`).  The pitch tracker (`penn`, a
         third-party neural network) runs outside the library: `tracks` =
@@ -729,19 +737,23 @@ class Engine:
         periodicity on the packed frame axis (`batch.pack_tracks`); the
         log2 / normalisation / row placement of core.py:94-106,123 happens
         on the device.  `config`: another configuration's feature switches
-        (`data.preprocess.mels.from_audio` asks for the mel rows alone)."""
+        (`data.preprocess.mels.from_audio` asks for the mel rows alone).
+        `out`: the caller's own rows [num_features, ld_frames] - rows of a
+        larger matrix, say (`data.preprocess.from_files_to_files` puts the
+        loudness row under the mel rows that way) - instead of the engine's
+        workspace."""
         config = config or self.config
         rows = config.num_features
-        out = self._buffer('features', rows, plan.ld_frames)
+        if out is None:
+            out = self._buffer('features', rows, plan.ld_frames)
+        elif out.shape[0] < rows or out.stride(0) != plan.ld_frames or \
+                out.dtype != torch.float32:
+            raise ValueError('features: out must be float32 rows of ld_frames')
         mel_row = 0 if config.mel_feature else -1
         loud_row = rows - 1 if config.loudness_feature else -1
         if config.pitch_feature or config.periodicity_feature:
             if tracks is None or tuple(tracks.shape) != (2, plan.ld_frames):
-                raise NotImplementedError(
-                    'pitch/periodicity features come from the third-party '
-                    '`penn` tracker; pass its outputs as tracks '
-                    '[2, ld_frames] (see core.from_alignments_and_audios '
-                    'pitch_tracker=)')
+                raise NotImplementedError(TRACKS_NEEDED)
             first = cfg.NUM_MELS if config.mel_feature else 0
             pitch_row = first if config.pitch_feature else -1
             periodicity_row = first + int(config.pitch_feature) \

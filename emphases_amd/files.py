@@ -143,18 +143,24 @@ class FileAudio:
 
 
 class FileBatch:
-    """`count` (alignment file, audio file) pairs opened by the library."""
+    """`count` (alignment file, audio file) pairs opened by the library.
+    `text_files` None: audio files alone (`data.preprocess`), every alignment
+    empty."""
 
     def __init__(self, text_files, audio_files, threads=None):
-        self.text_files = [str(file) for file in text_files]
         self.audio_files = [str(file) for file in audio_files]
-        self.count = len(self.text_files)
+        self.text_files = None if text_files is None else \
+            [str(file) for file in text_files]
+        self.count = len(self.audio_files)
+        if self.text_files is not None and len(self.text_files) != self.count:
+            raise ValueError('as many alignment files as audio files')
         self.threads = int(threads or THREADS)
         lib = runtime.library()
         self._lib = lib
         self._handle = ctypes.c_void_p()
-        self._text = (ctypes.c_char_p * max(self.count, 1))(
-            *[file.encode() for file in self.text_files])
+        self._text = None if self.text_files is None else \
+            (ctypes.c_char_p * max(self.count, 1))(
+                *[file.encode() for file in self.text_files])
         self._audio = (ctypes.c_char_p * max(self.count, 1))(
             *[file.encode() for file in self.audio_files])
         runtime.check(lib.emph_files_open(
@@ -433,3 +439,46 @@ class FileBatch:
         runtime.check(self._lib.emph_files_write(
             self._handle, which.ctypes.data, paths, flat.data_ptr(),
             first.ctypes.data, len(native), self.threads), 'emph_files_write')
+
+
+def write_tensors(paths, data, first, rows, columns, threads=None):
+    """`torch.save` of the float32 CPU tensors [rows[k], columns[k]] that lie
+    C-contiguous at float offset `first[k]` of `data` (a float32 host tensor
+    or array: a batch's pinned result buffer) to `paths[k]`, on the library's
+    file pool; parent directories are created (`mels.py:70-76`).  Returns
+    `[(k, reason)]` of the files that could not be written - a bad path does
+    not stop the others."""
+    count = len(paths)
+    first = np.ascontiguousarray(first, dtype=np.int64)
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    columns = np.ascontiguousarray(columns, dtype=np.int64)
+    if not len(first) == len(rows) == len(columns) == count:
+        raise ValueError('one offset and one shape per path')
+    if not count:
+        return []
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.float32 or not data.flags['C_CONTIGUOUS']:
+            raise ValueError('data must be contiguous float32')
+        address, floats = data.ctypes.data, data.size
+    else:
+        if data.dtype != torch.float32 or data.is_cuda or \
+                not data.is_contiguous():
+            raise ValueError('data must be a contiguous float32 host tensor')
+        address, floats = data.data_ptr(), data.numel()
+    if int(first.min()) < 0 or int(rows.min()) < 0 or \
+            int(columns.min()) < 0 or \
+            int((first + rows * columns).max()) > floats:
+        raise ValueError('a tensor lies outside data')
+    lib = runtime.library()
+    names = (ctypes.c_char_p * count)(
+        *[os.fspath(path).encode() for path in paths])
+    failed = lib.emph_files_write_tensors(
+        names, address, first.ctypes.data, rows.ctypes.data,
+        columns.ctypes.data, count, int(threads or THREADS))
+    if failed < 0:
+        runtime.check(failed, 'emph_files_write_tensors')
+    if not failed:
+        return []
+    reasons = [lib.emph_files_write_tensors_error(k).decode('utf-8', 'replace')
+               for k in range(count)]
+    return [(k, reason) for k, reason in enumerate(reasons) if reason]

@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -151,6 +151,9 @@ SIGNATURES = {
         _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _i32]),
     'emph_files_write': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32]),
+    'emph_files_write_tensors': (_c.c_int, [
+        _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32]),
+    'emph_files_write_tensors_error': (_c.c_char_p, [_i32]),
     'emph_plan_tiles': (_i64, [_ptr, _ptr, _i32, _i32, _i64, _i64, _ptr]),
     'emph_plan_batch': (_c.c_int, [
         _ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr,
@@ -160,6 +163,7 @@ SIGNATURES = {
         _ptr, _ptr, _ptr, _ptr, _i64, _ptr]),
     'emph_gather_columns': (_c.c_int, [
         _ptr, _i64, _ptr, _i64, _i32, _ptr, _i32, _ptr]),
+    'emph_unpack_rows': (_c.c_int, [_ptr, _i64, _ptr, _i32, _ptr, _ptr]),
     'emph_word_decoder_block': (_i32, [_i32, _i32, _i32]),
     'emph_word_decoder_tiles': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
     'emph_word_decoder_pack_size': (_i64, [_i32, _i32]),

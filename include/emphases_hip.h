@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 32
+#define EMPH_ABI_VERSION 33
 
 /* Segment-table fields */
 enum {
@@ -138,7 +138,9 @@ int emph_files_affinity(const int32_t* cpus, int32_t count);
 
 /* Parse text_paths[i] (.TextGrid) and walk the headers of audio_paths[i]
  * (.wav), i < count.  A file that fails is reported per file (emph_files_sizes
- * status, emph_files_error), not as an error of the call. */
+ * status, emph_files_error), not as an error of the call.  text_paths may be
+ * NULL: a batch of audio files alone (feature-cache preprocessing), every
+ * alignment empty. */
 int emph_files_open(const char* const* text_paths,
                     const char* const* audio_paths, int32_t count,
                     int32_t threads, emph_file_batch** batch);
@@ -175,6 +177,21 @@ int emph_files_read_audio(const emph_file_batch* batch, const int32_t* which,
 int emph_files_write(const emph_file_batch* batch, const int32_t* which,
                      const char* const* prefixes, const float* scores,
                      const int64_t* first, int32_t count, int32_t threads);
+
+/* torch.save of the float32 CPU tensor [rows[k]][columns[k]] (C-contiguous) at
+ * data + first[k] (HOST pointer, offsets in floats) to paths[k], k < count, on
+ * the file pool's threads; parent directories are created.  What
+ * emphases/data/preprocess/mels.py:62-86 and loudness.py:27-51 leave behind,
+ * for a batch of files.  A file that cannot be written is reported per file,
+ * not as an error of the call: the return value is the NUMBER of such files
+ * (0: all written; negative: EMPH_E*, nothing written), and
+ * emph_files_write_tensors_error(k) is the reason for paths[k] of the calling
+ * thread's last call ("" for a file that was written). */
+int emph_files_write_tensors(const char* const* paths, const float* data,
+                             const int64_t* first, const int64_t* rows,
+                             const int64_t* columns, int32_t count,
+                             int32_t threads);
+const char* emph_files_write_tensors_error(int32_t index);
 
 /* Integer tables of a batch plan built on the host (what emphases_amd/batch.py
  * builds with numpy; host arithmetic on the segment lengths and word bounds
@@ -538,6 +555,23 @@ int emph_output_layer(const float* x, int64_t ldx, const float* weight,
 int emph_gather_columns(const float* x, int64_t ldx, float* y, int64_t ldy,
                         int32_t channels, const int64_t* pieces,
                         int32_t n_pieces, void* stream);
+
+/* The packed feature matrix of a batch (emph_logmel: x [rows][ld], segments on
+ * multiples of 16 columns) taken apart into the C-contiguous tensors a feature
+ * cache holds (emphases/data/preprocess/mels.py:62-86, loudness.py:27-51), one
+ * launch for the whole batch.
+ *   table  int64 [n][5] on the DEVICE = (first column, frames, first row, rows,
+ *          destination offset in floats); entry k writes
+ *          out[dst + r * frames + f] = x[(row0 + r) * ld + col0 + f]
+ * A mel + loudness batch has two entries per file (rows 0..79 and row 80).
+ * Only the blocks named are written; destinations need no alignment.  It
+ * neither allocates nor synchronises.  The table is device memory, so the
+ * call itself refuses what it can see (a null pointer, a negative n or ld);
+ * an entry with a negative field, outside a row of x (col0 + frames > ld) or
+ * of 2^31 floats or more is skipped by the kernel.  The caller vouches for the
+ * rows of x and the size of out. */
+int emph_unpack_rows(const float* x, int64_t ld, const int64_t* table,
+                     int32_t n, float* out, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Fused word stage of the convolutional model                               */
