@@ -29,6 +29,7 @@ from . import batch
 from . import config as cfg
 from . import engine as engine_module
 from . import load
+from . import pipeline
 from . import runtime
 
 _ACTIVE = [cfg.DEFAULT]
@@ -232,29 +233,6 @@ def from_file_to_file(text_file, audio_file, output_prefix=None,
     _save(alignment_module.Alignment(text_file), scores, output_prefix)
 
 
-def files_to_scores(text_files, audio_files, session, batch_size=None,
-                    utterances_per_batch=256, deliver=None,
-                    deliver_batch=None, pitch_tracker=None):
-    """The loop of `core.py:169-179` over ragged batches of
-    `utterances_per_batch` files, two batches in flight.  A batch of files is
-    opened by the library in one call (`files.FileBatch`: TextGrids parsed and
-    WAVE headers walked on a pool of host threads), the samples of batch i+1
-    are read straight into the session's pinned staging buffer while batch i
-    computes, 16-bit PCM files travel to the device as 16-bit PCM, files that
-    are not at 16 kHz are resampled on the device (one submission per sample
-    rate).  Results: `deliver_batch(opened, local indices, global indices,
-    scores)` once per submission, or `deliver(index, alignment, scores)` per
-    file, in order within a batch."""
-    from . import files
-    text_files, audio_files = list(text_files), list(audio_files)
-    for file in text_files:
-        if not str(file).endswith(('.TextGrid', '.json')):
-            from_text_and_audio(None, None, None)
-    _files_to_scores(text_files, audio_files, session, batch_size,
-                     utterances_per_batch, deliver, deliver_batch,
-                     pitch_tracker)
-
-
 # `files_to_scores` appends (stage, batch, start, end) in perf_counter_ns here when
 # it is a list (tools/files_timeline.py): where the three stages of a batch run
 TIMELINE = None
@@ -265,20 +243,29 @@ def _stamp(stage, position, start):
         TIMELINE.append((stage, position, start, time.perf_counter_ns()))
 
 
-def _files_to_scores(text_files, audio_files, session, batch_size,
-                     utterances_per_batch, deliver, deliver_batch,
-                     pitch_tracker=None):
-    """Three stages run side by side, each on a thread of its own (what the
-    helpers call are library or numpy routines that leave the interpreter lock
-    alone; none of them enters a torch CPU parallel region):
+def files_to_scores(text_files, audio_files, session, batch_size=None,
+                    utterances_per_batch=256, deliver=None,
+                    deliver_batch=None, pitch_tracker=None):
+    """The loop of `core.py:169-179` over ragged batches of
+    `utterances_per_batch` files, two batches in flight.  16-bit PCM files
+    travel to the device as 16-bit PCM, files that are not at 16 kHz are
+    resampled on the device (one submission per sample rate).  Results:
+    `deliver_batch(opened, local indices, global indices, scores)` once per
+    submission, or `deliver(index, alignment, scores)` per file, in order
+    within a batch.
+
+    The batches go through the stages of `pipeline.run` (what they call are
+    library or numpy routines that leave the interpreter lock alone; none of
+    them enters a torch CPU parallel region):
 
         openers  batches i + 1 and i + 2 (two threads: an opener waits on the
                  library's pool and on the interpreter lock in turn, so one of
                  them delivered a batch per 4.9 ms against 2.5 ms alone,
-                 profiles/r5_files_timeline.txt): open + parse + header walk
-                 (`files.FileBatch`), the samples into a pinned buffer of the
-                 session (`read_all`), the plan (`batch.plan_batch`) and its
-                 metadata tables (`Engine.prepare`)
+                 profiles/r5_files_timeline.txt): a batch opened by the
+                 library in one call, TextGrids parsed and WAVE headers walked
+                 on its pool (`files.FileBatch`), the samples straight into a
+                 pinned buffer of the session (`read_all`), the plan
+                 (`batch.plan_batch`) and its tables (`Engine.prepare`)
         caller   batch i: DMA + kernels (`Session.submit`), then the scores
                  of batch i - 1
         writer   batch i - 1: `<prefix>.TextGrid` + `<prefix>.pt`
@@ -287,22 +274,28 @@ def _files_to_scores(text_files, audio_files, session, batch_size,
     keep busy (`files.stage_threads`): a cgroup that allows fewer CPUs than the
     machine shows FREEZES the process for the rest of the period when opener,
     writer, caller and the HIP runtime's threads together exceed the quota.
-    A failure anywhere still finishes and writes every batch submitted before
-    it - like the reference's loop (`core.py:169-179`), which leaves the
-    outputs of every file in front of the bad one - then raises."""
-    import collections
-    import concurrent.futures
+    A failure leaves the outputs of every batch submitted before it, as the
+    reference's loop leaves those of every file in front of the bad one."""
     from . import files
     from . import session as session_module
+    text_files, audio_files = list(text_files), list(audio_files)
+    for file in text_files:
+        if not str(file).endswith(('.TextGrid', '.json')):
+            from_text_and_audio(None, None, None)
     engine = session.engine
-    open_threads, write_threads = files.stage_threads(session_module.FILE_BUFFERS - 2)
+    ahead = session_module.FILE_BUFFERS - 2
+    open_threads, write_threads = files.stage_threads(ahead)
     # (the pitch tracker wants every utterance's samples on the host)
     tracked = engine.config.pitch_feature or engine.config.periodicity_feature
+    # (a quarter and a half batch at both ends, to ramp the pipeline up and down,
+    # was measured and is not faster: 57-58 ms against 54-57 for 4 096 files)
+    starts = list(range(0, len(text_files), utterances_per_batch))
 
-    def open_batch(first, last, turn):
+    def open_batch(turn):
         start = time.perf_counter_ns()
+        chunk = slice(starts[turn], starts[turn] + utterances_per_batch)
         opened = files.FileBatch(
-            text_files[first:last], audio_files[first:last], open_threads)
+            text_files[chunk], audio_files[chunk], open_threads)
         _stamp('open.parse', turn, start)
         begin = time.perf_counter_ns()
         dtype = None if tracked else opened.staged_format(cfg.SAMPLE_RATE)
@@ -351,8 +344,9 @@ def _files_to_scores(text_files, audio_files, session, batch_size,
         _stamp('open', turn, start)
         return opened, groups
 
-    def write(position, opened, chosen, indices, scores):
+    def write(position, job):
         start = time.perf_counter_ns()
+        opened, chosen, indices, scores = job
         opened.threads = write_threads
         if deliver_batch is not None:
             deliver_batch(opened, chosen, indices, scores)
@@ -361,96 +355,32 @@ def _files_to_scores(text_files, audio_files, session, batch_size,
                 deliver(index, opened.alignment(local), item)
         _stamp('write', position, start)
 
-    # (a quarter and a half batch at both ends, to ramp the pipeline up and down,
-    # was measured and is not faster: 57-58 ms against 54-57 for 4 096 files)
-    starts = list(range(0, len(text_files), utterances_per_batch))
-    ends = [min(first + utterances_per_batch, len(text_files))
-            for first in starts]
-    ahead = session_module.FILE_BUFFERS - 2
-    # the stages' threads (these two pools and the library's file pool: ours, not
-    # the caller's) next to the GPU: what they copy into pinned memory its DMA
-    # engine reads
-    # - when that node has room for them: the pools are sized from the whole CPU
-    # budget (`files.stage_threads`), and packed onto a few near CPUs they would
-    # lose more than the far socket costs.  The library's pool is shared by the
-    # process: it goes back to every allowed CPU when the call ends.
-    near = files.cpus_near(engine.device.index)
-    if near is not None and len(near) < open_threads + write_threads + 2:
-        near = None
-    settle, everywhere = None, None
-    if near is not None:
-        try:
-            everywhere = sorted(os.sched_getaffinity(0))
-            files.pool_near(near)
-        except (runtime.LibraryError, OSError):
-            near = everywhere = None                # (placement is a nicety)
-    if near is not None:
-        def settle():
-            try:
-                os.sched_setaffinity(0, near)       # (pid 0: this thread only)
-            except OSError:
-                pass                                # (a cpuset that changed: stay)
-    opener = concurrent.futures.ThreadPoolExecutor(
-        ahead, thread_name_prefix='emphases-open', initializer=settle)
-    writer = concurrent.futures.ThreadPoolExecutor(
-        1, thread_name_prefix='emphases-write', initializer=settle)
-    writes, in_flight, failure = [], [], None
+    def submit(position, job):
+        start = time.perf_counter_ns()
+        opened, groups = job
+        first = starts[position]
+        jobs = [(session.submit_staged(plan, audios)
+                 if type(audios) is session_module.Staged else
+                 session.submit(picked, audios, rate, batch_size, plan=plan,
+                                pitch_tracker=pitch_tracker),
+                 opened, chosen, range(first + chosen[0], first + chosen[-1] + 1)
+                 if type(chosen) is range else [first + i for i in chosen])
+                for rate, chosen, picked, audios, plan in groups]
+        _stamp('submit', position, start)
+        return jobs
 
-    def finish(jobs, drain=2):
-        for position, pending, opened, chosen, indices in jobs:
+    def collect(position, jobs):
+        for pending, opened, chosen, indices in jobs:
             start = time.perf_counter_ns()
             scores = pending.scores()
             _stamp('scores', position, start)
-            writes.append(writer.submit(
-                write, position, opened, chosen, indices, scores))
-        while len(writes) > drain:          # (errors surface; memory bounded)
-            writes.pop(0).result()
+            yield opened, chosen, indices, scores
 
-    def ask(position):
-        return opener.submit(
-            open_batch, starts[position], ends[position], position)
-
-    try:
-        opening = collections.deque(
-            ask(position) for position in range(min(ahead, len(starts))))
-        for position, first in enumerate(starts):
-            opened, groups = opening.popleft().result()
-            if position + ahead < len(starts):
-                opening.append(ask(position + ahead))
-            start = time.perf_counter_ns()
-            jobs = [(position,
-                     session.submit_staged(plan, audios)
-                     if type(audios) is session_module.Staged else
-                     session.submit(picked, audios, rate, batch_size, plan=plan,
-                                    pitch_tracker=pitch_tracker),
-                     opened, chosen, range(first + chosen[0], first + chosen[-1] + 1)
-                     if type(chosen) is range else [first + i for i in chosen])
-                    for rate, chosen, picked, audios, plan in groups]
-            _stamp('submit', position, start)
-            previous, in_flight = in_flight, jobs
-            finish(previous)
-    except BaseException as error:      # noqa: BLE001
-        failure = error
-    # what was submitted is finished and written whatever happened after it
-    for jobs in (in_flight,):
-        try:
-            finish(jobs, drain=0)
-        except BaseException as error:      # noqa: BLE001
-            failure = failure or error
-    for pending_write in writes:
-        try:
-            pending_write.result()
-        except BaseException as error:      # noqa: BLE001
-            failure = failure or error
-    opener.shutdown(wait=True, cancel_futures=True)
-    writer.shutdown(wait=True)
-    if everywhere is not None:
-        try:
-            files.pool_near(everywhere)
-        except runtime.LibraryError:
-            pass
-    if failure is not None:
-        raise failure
+    with pipeline.near_gpu(
+            engine.device.index, open_threads + write_threads + 2) as settle:
+        pipeline.run(len(starts), open_batch, submit, write, collect,
+                     openers=ahead, ahead=ahead, unwritten=2,
+                     initializer=settle)
 
 
 def from_files_to_files(text_files, audio_files, output_prefixes=None,

@@ -1,8 +1,6 @@
 """`emphases/data/preprocess/core.py` on the device: `from_audio` (71-125)
 and the feature cache of whole datasets (`datasets`, 13-68), a batch of files
 at a time."""
-import collections
-import concurrent.futures
 import dataclasses
 import functools
 import os
@@ -14,6 +12,7 @@ import torch
 from ... import batch
 from ... import config as cfg
 from ... import core
+from ... import pipeline
 from ... import runtime
 
 
@@ -279,7 +278,7 @@ def from_files_to_files(audio_files, mel_files=None, loudness_files=None,
 
     The reference runs one file at a time.  Here the mono 16 kHz files in
     16-bit PCM or float32 go in ragged batches of `files_per_batch`, two in
-    flight, through three stages on threads of their own:
+    flight, through the stages of `pipeline.run` (no `collect` here):
 
         opener   the samples of batches i + 1, i + 2 straight into pinned
                  memory (`files.FileBatch.read`), their plan (`batch_plan`),
@@ -415,6 +414,7 @@ def from_files_to_files(audio_files, mel_files=None, loudness_files=None,
             lane.done.record(lane.stream)
         job['lane'], job['result'] = lane, result
         _stamp('submit', position, begin)
+        return job
 
     def write(position, job):
         begin = time.perf_counter_ns()
@@ -433,65 +433,18 @@ def from_files_to_files(audio_files, mel_files=None, loudness_files=None,
         _stamp('write', position, begin)
         _raise_unwritten(failed)
 
-    # the stages' threads next to the GPU, as in `core._files_to_scores`
-    near = files.cpus_near(index)
-    if near is not None and len(near) < open_threads + write_threads + 2:
-        near = None
-    settle, everywhere = None, None
-    if near is not None:
-        try:
-            everywhere = sorted(os.sched_getaffinity(0))
-            files.pool_near(near)
-        except (runtime.LibraryError, OSError):
-            near = everywhere = None
-
-        def settle():
-            try:
-                os.sched_setaffinity(0, near)
-            except (OSError, TypeError):
-                pass
-    ahead = session_module.FILE_BUFFERS - 2
-    opener = concurrent.futures.ThreadPoolExecutor(
-        1, thread_name_prefix='emphases-open', initializer=settle)
-    writer = concurrent.futures.ThreadPoolExecutor(
-        1, thread_name_prefix='emphases-write', initializer=settle)
-    writes, failure = collections.deque(), None
     try:
-        opening = collections.deque(
-            opener.submit(open_batch, position)
-            for position in range(min(ahead, len(batches))))
-        for position in range(len(batches)):
-            job = opening.popleft().result()
-            # the lane's pinned result buffer and the staging buffer that the
-            # next opener takes are free once batch `position - 2` is written
-            while len(writes) >= len(session.lanes):
-                writes.popleft().result()
-            if position + ahead < len(batches):
-                opening.append(opener.submit(open_batch, position + ahead))
-            enqueue(position, job)
-            writes.append(writer.submit(write, position, job))
-    except BaseException as error:      # noqa: BLE001
-        failure = error
-    for pending in writes:
-        try:
-            pending.result()
-        except BaseException as error:      # noqa: BLE001
-            failure = failure or error
-    opener.shutdown(wait=True, cancel_futures=True)
-    writer.shutdown(wait=True)
-    for lane in session.lanes:
-        try:
+        with pipeline.near_gpu(
+                index, open_threads + write_threads + 2) as settle:
+            # (the lane's pinned result buffer and the staging buffer that the
+            # next opener takes are free once batch `position - 2` is written)
+            pipeline.run(len(batches), open_batch, enqueue, write, openers=1,
+                         ahead=session_module.FILE_BUFFERS - 2,
+                         unwritten=len(session.lanes) - 1, initializer=settle)
+    finally:
+        for lane in session.lanes:
             lane.stream.synchronize()
-        except Exception as error:      # noqa: BLE001
-            failure = failure or error
-    if everywhere is not None:
-        try:
-            files.pool_near(everywhere)
-        except runtime.LibraryError:
-            pass
-    opened.close()
-    if failure is not None:
-        raise failure
+        opened.close()
     begin = time.perf_counter_ns()
     for i in slow:
         _per_file(audio_files[i],
