@@ -33,3 +33,5 @@ from . import evaluate  # noqa: F401,E402
 from . import ops  # noqa: F401,E402
 # emphases.data.preprocess.{from_audio, mels.from_audio, loudness.from_audio}
 from . import data  # noqa: F401,E402
+# one training step of the convolution model (emphases.train, without the loop)
+from . import train  # noqa: F401,E402

@@ -1,0 +1,316 @@
+// The small kernels of the training step of the convolution model: loss and
+// its gradient, the backward of the output projection, of the activation and
+// of the frame -> word reduce, the Adam update, and the gather that rebuilds
+// the MFMA weight packs from the flat parameter buffer.  (The heavy one, the
+// weight gradient of a Conv1d, is csrc/conv_grad.hip; the data gradient is
+// emph_conv1d itself on a transposed, tap-flipped pack.)
+//
+// Replaces what autograd and torch.optim.Adam do for the reference's loop
+// (emphases/train/core.py:111-142): loss 315-353, `scaler.scale(loss)
+// .backward()` 136, `scaler.step(optimizer)` 139 - in fp32, no GradScaler.
+//
+// Everything here is deterministic: no floating-point atomics, every
+// reduction in a fixed order that does not depend on the launch.
+#include <math.h>
+
+#include "common.h"
+
+namespace emph {
+
+__global__ __launch_bounds__(256) void take_kernel(
+    const float* __restrict__ src, const int32_t* __restrict__ index,
+    float* __restrict__ out, int64_t count) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int32_t from = index[i];
+    out[i] = from < 0 ? 0.f : src[from];
+}
+
+// Sum of `value` over the 256 threads of the block, in a fixed order (a
+// binary tree over thread indices); valid in thread 0.
+template <typename T>
+__device__ __forceinline__ T block_sum(T value, T* shared) {
+    shared[threadIdx.x] = value;
+    __syncthreads();
+#pragma unroll
+    for (int width = 128; width > 0; width >>= 1) {
+        if (static_cast<int>(threadIdx.x) < width)
+            shared[threadIdx.x] += shared[threadIdx.x + width];
+        __syncthreads();
+    }
+    const T total = shared[0];
+    __syncthreads();
+    return total;
+}
+
+// One workgroup: thread i owns columns i, i + 256, ... of the packed word
+// axis (in that order), then the fixed tree.  The loss is a few thousand
+// terms at the most, so each term and the sum are formed in double and the
+// mean is rounded to float once: the scalar carries the error of the logits
+// alone, not another ulp or two of its own.  The gradient stays in float.
+__global__ __launch_bounds__(256) void loss_grad_kernel(
+    const float* __restrict__ logits, const float* __restrict__ targets,
+    const int32_t* __restrict__ word_segment, int64_t columns, int64_t valid_words,
+    int form, float* __restrict__ loss, float* __restrict__ dlogit) {
+    // (the gradient's 1 / N is a float, as autograd's is; the mean divides)
+    const float inverse_count = static_cast<float>(1.0 / static_cast<double>(valid_words));
+    __shared__ double shared[256];
+    double sum = 0.;
+    for (int64_t column = threadIdx.x; column < columns; column += 256) {
+        float gradient = 0.f;
+        if (word_segment[column] >= 0) {
+            const float z = logits[column], y = targets[column];
+            if (form == 0) {
+                // binary_cross_entropy_with_logits, the stable form of ATen
+                const double wide = z;
+                sum += fmax(wide, 0.) - wide * y + log1p(exp(-fabs(wide)));
+                gradient = (1.f / (1.f + expf(-z)) - y) * inverse_count;
+            } else {
+                const float d = z - y;
+                const double wide = static_cast<double>(z) - y;
+                sum += wide * wide;
+                gradient = 2.f * d * inverse_count;
+            }
+        }
+        dlogit[column] = gradient;
+    }
+    const double total = block_sum(sum, shared);
+    if (threadIdx.x == 0) loss[0] = static_cast<float>(total / static_cast<double>(valid_words));
+}
+
+// dx of Conv1d(channels, 1, 3): a thread per (channel, column).
+__global__ __launch_bounds__(256) void output_backward_data_kernel(
+    const float* __restrict__ dlogit, const float* __restrict__ weight,
+    const int32_t* __restrict__ word_segment, int channels, int64_t columns,
+    float* __restrict__ dx, int64_t ldx) {
+    const int64_t index = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (index >= columns * channels) return;
+    const int c = static_cast<int>(index / columns);
+    const int64_t column = index - c * columns;
+    const int segment = word_segment[column];
+    float value = 0.f;
+    if (segment >= 0) {
+        // dx[c][w] = sum_j W[c][j] dlogit[w - j + 1], inside the segment
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int64_t from = column - j + 1;
+            if (from >= 0 && from < columns && word_segment[from] == segment)
+                value = fmaf(weight[c * 3 + j], dlogit[from], value);
+        }
+    }
+    dx[static_cast<int64_t>(c) * ldx + column] = value;
+}
+
+// dW and db of Conv1d(channels, 1, 3): block c < channels sums the three taps
+// of channel c, block `channels` sums the bias.
+__global__ __launch_bounds__(256) void output_backward_weight_kernel(
+    const float* __restrict__ dlogit, const float* __restrict__ x, int64_t ldx,
+    const int32_t* __restrict__ word_segment, int channels, int64_t columns,
+    float* __restrict__ dweight, float* __restrict__ dbias) {
+    __shared__ float shared[256];
+    const int c = blockIdx.x;
+    float sum[3] = {0.f, 0.f, 0.f};
+    for (int64_t column = threadIdx.x; column < columns; column += 256) {
+        const int segment = word_segment[column];
+        if (segment < 0) continue;
+        const float g = dlogit[column];
+        if (c == channels) {
+            sum[0] += g;
+            continue;
+        }
+        // dW[c][j] = sum_w dlogit[w] x[c][w + j - 1], x zero outside the segment
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int64_t from = column + j - 1;
+            if (from >= 0 && from < columns && word_segment[from] == segment)
+                sum[j] = fmaf(g, x[static_cast<int64_t>(c) * ldx + from], sum[j]);
+        }
+    }
+    if (c == channels) {
+        const float total = block_sum(sum[0], shared);
+        if (threadIdx.x == 0) dbias[0] = total;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float total = block_sum(sum[j], shared);
+        if (threadIdx.x == 0) dweight[c * 3 + j] = total;
+    }
+}
+
+__global__ __launch_bounds__(256) void activation_backward_kernel(
+    const float4* __restrict__ y, float4* __restrict__ gradient, int64_t quads) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= quads) return;
+    const float4 out = y[i];
+    float4 g = gradient[i];
+    // (a select, not a product: what lies outside the segments is undefined)
+    g.x = out.x > 0.f ? g.x : 0.f;
+    g.y = out.y > 0.f ? g.y : 0.f;
+    g.z = out.z > 0.f ? g.z : 0.f;
+    g.w = out.w > 0.f ? g.w : 0.f;
+    gradient[i] = g;
+}
+
+// One workgroup per 64-frame tile: 64 frames x 4 channel lanes.  A thread
+// finds the word of its frame by bisection over the segment's (sorted,
+// non-overlapping) words, then walks the channels.
+__global__ __launch_bounds__(256) void segment_broadcast_kernel(
+    const float* __restrict__ dword, int64_t ldw, const int32_t* __restrict__ bounds,
+    float* __restrict__ dx, int64_t ldx, int channels, const int64_t* __restrict__ seg,
+    const int32_t* __restrict__ tiles, int mode) {
+    const Tile tile = load_tile(tiles, blockIdx.x);
+    const int t = tile.first + (threadIdx.x & 63);
+    if (t >= tile.count) return;
+    const int64_t* row = seg + static_cast<int64_t>(tile.segment) * EMPH_SEG_FIELDS;
+    const int64_t word_off = row[EMPH_SEG_WORD_OFF];
+    const int words = static_cast<int>(row[EMPH_SEG_WORDS]);
+    // the last word whose start is <= t
+    int low = 0, high = words;
+    while (low < high) {
+        const int middle = (low + high) >> 1;
+        if (bounds[word_off + middle] <= t) low = middle + 1; else high = middle;
+    }
+    const int word = low - 1;
+    float scale = 0.f;
+    int64_t column = 0;
+    if (word >= 0) {
+        column = word_off + word;
+        const int start = bounds[column], end = bounds[ldw + column];
+        if (t < end)
+            scale = mode == EMPH_REDUCE_AVERAGE ? 1.f / static_cast<float>(end - start) : 1.f;
+    }
+    float* out = dx + tile.offset + t;
+    for (int c = threadIdx.x >> 6; c < channels; c += 4) {
+        float value = 0.f;
+        if (scale != 0.f) {
+            value = dword[static_cast<int64_t>(c) * ldw + column];
+            if (mode == EMPH_REDUCE_AVERAGE) value *= scale;
+        }
+        out[static_cast<int64_t>(c) * ldx] = value;
+    }
+}
+
+// torch.optim.Adam, single-tensor arithmetic (torch/optim/adam.py,
+// _single_tensor_adam): lerp, mul + addcmul, sqrt / sqrt(bc2) + eps, addcdiv.
+// weight1 = 1 - beta1 and weight2 = 1 - beta2 are formed in double and rounded
+// once, as torch's Python scalars are: 1.f - 0.999f is 2e-6 off 0.001f.
+__global__ __launch_bounds__(256) void adam_step_kernel(
+    float* __restrict__ parameter, const float* __restrict__ gradient,
+    float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, int64_t count,
+    float weight1, float beta2, float weight2, float step_size, float correction2_sqrt,
+    float eps) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float g = gradient[i];
+    const float m = exp_avg[i] + weight1 * (g - exp_avg[i]);
+    const float v = exp_avg_sq[i] * beta2 + weight2 * g * g;
+    exp_avg[i] = m;
+    exp_avg_sq[i] = v;
+    const float denominator = sqrtf(v) / correction2_sqrt + eps;
+    parameter[i] = parameter[i] - step_size * (m / denominator);
+}
+
+}  // namespace emph
+
+using namespace emph;
+
+extern "C" {
+
+int emph_take(const float* src, const int32_t* index, float* out, int64_t count,
+              void* stream) {
+    if (count == 0) return EMPH_OK;
+    EMPH_REQUIRE(src && index && out, EMPH_EINVAL, "emph_take: null pointer");
+    EMPH_REQUIRE(count > 0 && count < (int64_t{1} << 39), EMPH_ERANGE,
+                 "emph_take: count out of range");
+    EMPH_LAUNCH(take_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256),
+                0, static_cast<hipStream_t>(stream), src, index, out, count);
+    return check_launch("emph_take");
+}
+
+int emph_loss_grad(const float* logits, const float* targets,
+                   const int32_t* word_segment, int64_t columns, int64_t valid_words,
+                   int32_t form, float* loss, float* dlogit, void* stream) {
+    EMPH_REQUIRE(logits && targets && word_segment && loss && dlogit, EMPH_EINVAL,
+                 "emph_loss_grad: null pointer");
+    EMPH_REQUIRE(form == 0 || form == 1, EMPH_EINVAL,
+                 "emph_loss_grad: form %d (0 = bce, 1 = mse)", form);
+    EMPH_REQUIRE(columns > 0 && valid_words > 0 && valid_words <= columns, EMPH_EINVAL,
+                 "emph_loss_grad: bad shape");
+    EMPH_LAUNCH(loss_grad_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream),
+                logits, targets, word_segment, columns, valid_words, form, loss, dlogit);
+    return check_launch("emph_loss_grad");
+}
+
+int emph_output_layer_backward(const float* dlogit, const float* x, int64_t ldx,
+                               const float* weight, const int32_t* word_segment,
+                               int32_t channels, int32_t kernel_size, int64_t columns,
+                               float* dweight, float* dbias, float* dx, int64_t ld_dx,
+                               void* stream) {
+    EMPH_REQUIRE(dlogit && x && weight && word_segment && dweight && dbias && dx,
+                 EMPH_EINVAL, "emph_output_layer_backward: null pointer");
+    EMPH_REQUIRE(kernel_size == 3, EMPH_ERANGE,
+                 "emph_output_layer_backward: kernel_size %d (3)", kernel_size);
+    EMPH_REQUIRE(channels > 0 && channels <= 1024 && columns > 0 && columns <= ldx &&
+                     columns <= ld_dx,
+                 EMPH_EINVAL, "emph_output_layer_backward: bad shape");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EMPH_LAUNCH(output_backward_weight_kernel, dim3(channels + 1), dim3(256), 0, s, dlogit,
+                x, ldx, word_segment, channels, columns, dweight, dbias);
+    if (int status = check_launch("emph_output_layer_backward")) return status;
+    const int64_t threads = columns * channels;
+    EMPH_LAUNCH(output_backward_data_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)),
+                dim3(256), 0, s, dlogit, weight, word_segment, channels, columns, dx, ld_dx);
+    return check_launch("emph_output_layer_backward");
+}
+
+int emph_activation_backward(const float* y, float* gradient, int64_t count,
+                             int32_t activation, void* stream) {
+    if (count == 0) return EMPH_OK;
+    EMPH_REQUIRE(y && gradient, EMPH_EINVAL, "emph_activation_backward: null pointer");
+    EMPH_REQUIRE(activation == EMPH_ACT_RELU, EMPH_EINVAL,
+                 "emph_activation_backward: activation %d (relu only)", activation);
+    EMPH_REQUIRE(count > 0 && count % 4 == 0 &&
+                     (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
+                     (reinterpret_cast<uintptr_t>(gradient) & 15) == 0,
+                 EMPH_EINVAL, "emph_activation_backward: count and pointers in 16-byte units");
+    const int64_t quads = count / 4;
+    EMPH_LAUNCH(activation_backward_kernel, dim3(static_cast<unsigned>((quads + 255) / 256)),
+                dim3(256), 0, static_cast<hipStream_t>(stream),
+                reinterpret_cast<const float4*>(y), reinterpret_cast<float4*>(gradient), quads);
+    return check_launch("emph_activation_backward");
+}
+
+int emph_segment_broadcast(const float* dword, int64_t ldw, const int32_t* bounds,
+                           float* dx, int64_t ldx, int32_t channels, const int64_t* seg,
+                           const int32_t* tiles, int32_t n_tiles, int32_t mode,
+                           void* stream) {
+    if (n_tiles == 0) return EMPH_OK;
+    EMPH_REQUIRE(dword && bounds && dx && seg && tiles, EMPH_EINVAL,
+                 "emph_segment_broadcast: null pointer");
+    EMPH_REQUIRE(mode == EMPH_REDUCE_SUM || mode == EMPH_REDUCE_AVERAGE, EMPH_EINVAL,
+                 "emph_segment_broadcast: mode %d (sum or average)", mode);
+    EMPH_REQUIRE(channels > 0 && n_tiles > 0, EMPH_EINVAL,
+                 "emph_segment_broadcast: bad shape");
+    EMPH_LAUNCH(segment_broadcast_kernel, dim3(n_tiles), dim3(256), 0,
+                static_cast<hipStream_t>(stream), dword, ldw, bounds, dx, ldx, channels, seg,
+                tiles, mode);
+    return check_launch("emph_segment_broadcast");
+}
+
+int emph_adam_step(float* parameter, const float* gradient, float* exp_avg,
+                   float* exp_avg_sq, int64_t count, double beta1, double beta2,
+                   float step_size, float correction2_sqrt, float eps, void* stream) {
+    if (count == 0) return EMPH_OK;
+    EMPH_REQUIRE(parameter && gradient && exp_avg && exp_avg_sq, EMPH_EINVAL,
+                 "emph_adam_step: null pointer");
+    EMPH_REQUIRE(count > 0 && count < (int64_t{1} << 39), EMPH_ERANGE,
+                 "emph_adam_step: count out of range");
+    EMPH_LAUNCH(adam_step_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256),
+                0, static_cast<hipStream_t>(stream), parameter, gradient, exp_avg, exp_avg_sq,
+                count, static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
+                static_cast<float>(1.0 - beta2), step_size, correction2_sqrt, eps);
+    return check_launch("emph_adam_step");
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -193,6 +193,22 @@ SIGNATURES = {
         _ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _f32, _i64, _i64, _ptr]),
     'emph_quantile_spreads': (_c.c_int, [
         _ptr, _i64, _ptr, _i64, _i32, _ptr, _ptr, _ptr, _i64, _ptr]),
+    'emph_take': (_c.c_int, [_ptr, _ptr, _ptr, _i64, _ptr]),
+    'emph_loss_grad': (_c.c_int, [
+        _ptr, _ptr, _ptr, _i64, _i64, _i32, _ptr, _ptr, _ptr]),
+    'emph_output_layer_backward': (_c.c_int, [
+        _ptr, _ptr, _i64, _ptr, _ptr, _i32, _i32, _i64, _ptr, _ptr, _ptr,
+        _i64, _ptr]),
+    'emph_activation_backward': (_c.c_int, [_ptr, _ptr, _i64, _i32, _ptr]),
+    'emph_segment_broadcast': (_c.c_int, [
+        _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _i32, _i32, _ptr]),
+    'emph_conv_weight_grad_parts': (_i32, [_i32]),
+    'emph_conv_weight_grad': (_c.c_int, [
+        _ptr, _i64, _ptr, _i64, _i32, _i32, _i32, _ptr, _i32, _i32, _ptr,
+        _ptr, _ptr, _ptr]),
+    'emph_adam_step': (_c.c_int, [
+        _ptr, _ptr, _ptr, _ptr, _i64, _c.c_double, _c.c_double, _f32, _f32,
+        _f32, _ptr]),
 }
 
 _library = None

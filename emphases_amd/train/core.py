@@ -1,0 +1,569 @@
+"""The training step of the convolution model.
+
+What the reference does per batch (`emphases/train/core.py:105-142`: forward
+in train mode, `loss`, `backward`, `optimizer.step`) as launches of the HIP
+library on one stream.  Deliberate, documented deviations:
+
+* float32 throughout: no `torch.autocast`, no `GradScaler`
+  (`train/core.py:78,111,136-142`) - as inference (`core.inference_context`);
+* every utterance is trained alone, with its own zero halo, exactly as
+  inference runs it; the reference's padded batch leaks bias + ReLU of the
+  padding into the last frames and words of every shorter utterance
+  (`model/layers/convolution.py:35-37` ignores lengths).  The loss is the mean
+  over all valid words of the batch, as the reference's masked loss is.
+
+All parameters live in ONE flat device buffer in `weights.parameter_shapes`
+order (the order of `Model.parameters()`); gradients and the two Adam moments
+are buffers of the same shape.  The MFMA weight packs of the forward kernel
+(`emph_conv1d`) and of the data gradient (the same kernel on
+W'[ci][co][j] = W[co][ci][2 - j]) are rebuilt after every update by ONE
+gather launch (`emph_take`) through a table made once on the host.
+"""
+import collections
+import math
+import os
+
+import numpy as np
+import torch
+
+from .. import config as cfg
+from .. import core as api
+from .. import runtime
+from .. import weights as weights_module
+
+FRAME_TILE = 64      # emph_conv1d, emph_conv_weight_grad, emph_segment_broadcast
+WORD_TILE = 32       # emph_conv1d on the word axis
+GRAD_TILE = 64       # emph_conv_weight_grad on either axis
+
+
+def check_supported(config):
+    """NotImplementedError, naming the field, for a configuration the step does
+    not cover - before anything is allocated or launched."""
+    def refuse(field, supported):
+        raise NotImplementedError(
+            f'the training step supports {field} {supported} only, not '
+            f'{field}={getattr(config, field)!r}')
+    if config.method != 'neural':
+        refuse('method', "'neural'")
+    if config.architecture != 'convolution':
+        refuse('architecture', "'convolution'")
+    if config.downsample_location != 'intermediate':
+        refuse('downsample_location', "'intermediate'")
+    if config.downsample_method not in ('sum', 'average'):
+        refuse('downsample_method', "'sum' or 'average'")
+    if config.activation != 'relu':
+        refuse('activation', "'relu'")
+    if config.loss not in ('bce', 'mse'):
+        refuse('loss', "'bce' or 'mse'")
+    if config.channels != 80:
+        refuse('channels', '80')
+    if config.encoder_kernel_size != 3:
+        refuse('encoder_kernel_size', '3')
+    if config.decoder_kernel_size != 3:
+        refuse('decoder_kernel_size', '3')
+    if not 0 <= config.layers <= 16:
+        refuse('layers', '0..16')
+    if not config.mel_feature:
+        refuse('mel_feature', 'True (80..83 input features)')
+
+
+def layer_names(config):
+    """The Conv1d(., 80, 3) layers in forward order."""
+    return ['input_layer'] + [
+        f'{prefix}.{2 * i}' for prefix in ('frame_encoder', 'word_decoder')
+        for i in range(config.layers)]
+
+
+def parameter_offsets(config):
+    """name -> (first element, shape) in the flat parameter buffer."""
+    offsets = collections.OrderedDict()
+    cursor = 0
+    for name, shape in weights_module.parameter_shapes(config).items():
+        offsets[name] = (cursor, tuple(shape))
+        cursor += int(np.prod(shape))
+    return offsets, cursor
+
+
+def initial_state(config=cfg.DEFAULT, seed=0):
+    """Bitwise the parameters of the reference's `emphases.Model()` after
+    `torch.manual_seed(seed)`: `torch.nn.Conv1d` modules built on the CPU in
+    the reference's construction order (`model/core.py:16-37`,
+    `model/layers/convolution.py:22-33`).  The caller's generator is left
+    as it was."""
+    check_supported(config)
+    state = collections.OrderedDict()
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+
+        def conv(name, c_in, c_out, kernel_size):
+            module = torch.nn.Conv1d(
+                c_in, c_out, kernel_size=kernel_size, padding='same')
+            state[f'{name}.weight'] = module.weight.detach().numpy().copy()
+            state[f'{name}.bias'] = module.bias.detach().numpy().copy()
+        conv('input_layer', config.num_features, config.channels,
+             config.encoder_kernel_size)
+        for prefix, kernel_size in (
+                ('frame_encoder', config.encoder_kernel_size),
+                ('word_decoder', config.decoder_kernel_size)):
+            for i in range(config.layers):
+                conv(f'{prefix}.{2 * i}', config.channels, config.channels,
+                     kernel_size)
+        conv('output_layer', config.channels, 1, config.decoder_kernel_size)
+    assert list(state) == list(weights_module.parameter_shapes(config))
+    return state
+
+
+def _pack_indices(indices):
+    """`emph_conv_pack` of an index array [c_out, c_in, k] (int, < 2^24): the
+    pack is a pure permutation with zero padding, so packing the indices + 1
+    gives, minus 1, where every element of a pack comes from (-1: padding)."""
+    assert indices.max() + 1 < 1 << 24
+    packed = runtime.conv_pack((indices + 1).astype(np.float32))
+    return packed.astype(np.int64) - 1
+
+
+def gather_tables(config=cfg.DEFAULT):
+    """The `emph_take` table of every pack of a step: int32 `index` into the
+    flat parameter buffer (-1: zero), and {layer: (first, size)} of the forward
+    packs (every layer) and of the data-gradient packs
+    W'[ci][co][j] = W[co][ci][k - 1 - j] (every layer but the input layer,
+    whose input needs no gradient)."""
+    check_supported(config)
+    offsets, _ = parameter_offsets(config)
+    pieces, forward, backward = [], {}, {}
+    cursor = 0
+    for direction, table in (('forward', forward), ('backward', backward)):
+        for name in layer_names(config):
+            if direction == 'backward' and name == 'input_layer':
+                continue
+            first, shape = offsets[f'{name}.weight']
+            indices = first + np.arange(
+                int(np.prod(shape)), dtype=np.int64).reshape(shape)
+            if direction == 'backward':
+                indices = np.ascontiguousarray(
+                    indices.transpose(1, 0, 2)[:, :, ::-1])
+            piece = _pack_indices(indices)
+            table[name] = (cursor, piece.size)
+            pieces.append(piece)
+            cursor += piece.size
+    index = np.concatenate(pieces).astype(np.int32)
+    return {'index': index, 'forward': forward, 'backward': backward}
+
+
+def check_batch(features, frame_lengths, word_bounds, word_lengths, targets,
+                config=cfg.DEFAULT):
+    """ValueError for a malformed batch (the first five items of the
+    reference's `emphases.data.collate`), before any launch.  Returns the
+    lengths as lists of int and the bounds as int64 numpy [B, 2, Wmax]."""
+    if features.dim() != 3 or features.shape[1] != config.num_features:
+        raise ValueError(
+            f'features must be [B, {config.num_features}, T], not '
+            f'{tuple(features.shape)}')
+    items = features.shape[0]
+    frames = [int(n) for n in frame_lengths]
+    words = [int(n) for n in word_lengths]
+    if len(frames) != items or len(words) != items or \
+            word_bounds.shape[0] != items or targets.shape[0] != items:
+        raise ValueError('the batch items disagree on the batch size')
+    if word_bounds.dim() != 3 or word_bounds.shape[1] != 2:
+        raise ValueError('word_bounds must be [B, 2, W]')
+    if targets.dim() != 3 or targets.shape[1] != 1:
+        raise ValueError('targets must be [B, 1, W]')
+    bounds = np.asarray(word_bounds.cpu(), dtype=np.int64)
+    for index, (count, length) in enumerate(zip(frames, words)):
+        if not 1 <= count <= features.shape[2]:
+            raise ValueError(
+                f'item {index}: frame length {count} outside the features '
+                f'(1..{features.shape[2]})')
+        if not 0 <= length <= bounds.shape[2]:
+            raise ValueError(
+                f'item {index}: word length {length} outside word_bounds')
+        if length > targets.shape[2]:
+            raise ValueError(
+                f'item {index}: targets hold {targets.shape[2]} words, '
+                f'word_lengths asks for {length}')
+        starts, ends = bounds[index, 0, :length], bounds[index, 1, :length]
+        if np.any(ends <= starts):
+            raise ValueError(f'item {index}: a word with end <= start')
+        if np.any(starts < 0) or np.any(ends > count):
+            raise ValueError(
+                f'item {index}: word bounds past its {count} frames')
+        if np.any(starts[1:] < ends[:-1]):
+            raise ValueError(
+                f'item {index}: words overlap or are not in order')
+    if sum(words) == 0:
+        raise ValueError('the batch has no word')
+    return frames, words, bounds
+
+
+def adam_state_dict(config, steps, exp_avg, exp_avg_sq, lr=1e-3,
+                    betas=(0.9, 0.999), eps=1e-8):
+    """`torch.optim.Adam.state_dict()` layout from the flat CPU moment
+    buffers: parameter i of `Model.parameters()` order under key i (no state
+    before the first step, as torch), the param group of this torch's Adam."""
+    offsets, _ = parameter_offsets(config)
+    shells = [torch.nn.Parameter(torch.zeros(shape))
+              for _, shape in offsets.values()]
+    template = torch.optim.Adam(
+        shells, lr=lr, betas=tuple(betas), eps=eps).state_dict()
+    state = {}
+    if steps:
+        for index, (first, shape) in enumerate(offsets.values()):
+            size = int(np.prod(shape))
+            state[index] = {
+                'step': torch.tensor(float(steps)),
+                'exp_avg': exp_avg[first:first + size].view(shape).clone(),
+                'exp_avg_sq':
+                    exp_avg_sq[first:first + size].view(shape).clone()}
+    return {'state': state, 'param_groups': template['param_groups']}
+
+
+def write_checkpoint(path, model, optimizer, epoch=0, step=0, score=0.,
+                     best=0.):
+    """The dict of `torchutil.checkpoint.save(file, model, optimizer,
+    **kwargs)`: the keys of the reference's shipped checkpoint.pt."""
+    torch.save({
+        'epoch': epoch, 'step': step, 'score': score, 'best': best,
+        'model': model, 'optimizer': optimizer}, os.fspath(path))
+
+
+class Batch:
+    """A collated batch on the device in packed ragged form (`Trainer.prepare`):
+    the plan, its metadata, the features [C, ld_frames] and the targets
+    [ld_words]."""
+
+    def __init__(self, plan, meta, features, targets):
+        self.plan = plan
+        self.meta = meta
+        self.features = features
+        self.targets = targets
+
+
+class Trainer:
+    """`Trainer(...).step(*batch[:5])` is one iteration of the reference's loop
+    (`train/core.py:105-142`) for the convolution model; see the module
+    docstring for the two deviations."""
+
+    def __init__(self, config=None, checkpoint=None, gpu=None, lr=1e-3,
+                 betas=(0.9, 0.999), eps=1e-8, seed=0):
+        """checkpoint: None (the reference's initialisation under `seed`), a
+        state dict, or a file `weights.load` reads; a file written by `save`
+        also restores the Adam moments and the step count."""
+        self.config = config = config or api.active_config()
+        check_supported(config)
+        self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
+        self.steps = 0
+        optimizer = None
+        if checkpoint is None:
+            state = initial_state(config, seed)
+        else:
+            if not isinstance(checkpoint, dict) and \
+                    not str(checkpoint).endswith('.npz'):
+                checkpoint = torch.load(
+                    os.fspath(checkpoint), map_location='cpu',
+                    weights_only=False)
+            if isinstance(checkpoint, dict) and 'model' in checkpoint:
+                optimizer = checkpoint.get('optimizer')
+                checkpoint = checkpoint['model']
+            state = weights_module.load(checkpoint, config)
+        self.offsets, self.count = parameter_offsets(config)
+        tables = gather_tables(config)
+        self.device = runtime.require_gpu(gpu)
+        self.lib = runtime.library()
+        with torch.cuda.device(self.device):
+            flat = np.concatenate([state[name].ravel() for name in self.offsets])
+            self.parameters = torch.from_numpy(flat).to(self.device)
+            self.gradients = torch.zeros_like(self.parameters)
+            self.exp_avg = torch.zeros_like(self.parameters)
+            self.exp_avg_sq = torch.zeros_like(self.parameters)
+            if optimizer is not None and optimizer.get('state'):
+                self._restore(optimizer)
+            self.take_index = torch.from_numpy(tables['index']).to(self.device)
+            self.packs = torch.zeros(
+                tables['index'].size, dtype=torch.float32, device=self.device)
+            self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self._forward_packs = tables['forward']
+            self._backward_packs = tables['backward']
+            self._workspace = {}
+            self._repack()
+
+    ###########################################################################
+    # State
+    ###########################################################################
+
+    def _view(self, buffer, name):
+        first, shape = self.offsets[name]
+        return buffer[first:first + int(np.prod(shape))].view(shape)
+
+    def _restore(self, optimizer):
+        moments = optimizer['state']
+        steps = set()
+        for index, name in enumerate(self.offsets):
+            entry = moments[index]
+            self._view(self.exp_avg, name).copy_(entry['exp_avg'])
+            self._view(self.exp_avg_sq, name).copy_(entry['exp_avg_sq'])
+            steps.add(int(entry['step']))
+        if len(steps) != 1:
+            raise ValueError('the optimizer state holds several step counts')
+        self.steps = steps.pop()
+        group = optimizer['param_groups'][0]
+        self.lr, self.eps = float(group['lr']), float(group['eps'])
+        self.betas = tuple(float(b) for b in group['betas'])
+
+    def state_dict(self):
+        """The parameters under the reference's names and shapes (CPU)."""
+        flat = self.parameters.cpu()
+        return collections.OrderedDict(
+            (name, self._view(flat, name).clone()) for name in self.offsets)
+
+    def optimizer_state_dict(self):
+        """`torch.optim.Adam.state_dict()` of the reference's optimizer
+        (`train/core.py:48`): parameters in `Model.parameters()` order."""
+        return adam_state_dict(
+            self.config, self.steps, self.exp_avg.cpu(), self.exp_avg_sq.cpu(),
+            self.lr, self.betas, self.eps)
+
+    def save(self, path, epoch=0, step=None, score=0., best=0.):
+        """The file `torchutil.checkpoint.save` writes in the reference's loop
+        (`train/core.py:162-169,189-196`): every inference entry point takes it
+        as `checkpoint=`, `Trainer(checkpoint=path)` resumes from it."""
+        write_checkpoint(
+            path, self.state_dict(), self.optimizer_state_dict(), epoch,
+            self.steps if step is None else step, score, best)
+
+    ###########################################################################
+    # Batches
+    ###########################################################################
+
+    def prepare(self, features, frame_lengths, word_bounds, word_lengths,
+                targets):
+        """Validate a collated batch (host or device tensors) and lay it out
+        on the device: one copy of the integer metadata, one gather launch
+        each for the features and the targets."""
+        config = self.config
+        frames, words, bounds = check_batch(
+            features, frame_lengths, word_bounds, word_lengths, targets,
+            config)
+        plan = api._packed_plan(frames, torch.from_numpy(bounds), words)
+        requests = [(runtime.AXIS_FRAMES, FRAME_TILE),
+                    (runtime.AXIS_WORDS, WORD_TILE),
+                    (runtime.AXIS_WORDS, GRAD_TILE)]
+        host, offsets = plan.pack_metadata(list(dict.fromkeys(requests)))
+        # emph_gather_columns pieces: (source column, length, target column,
+        # columns to write; the rest zero) of every item, frames then words
+        align = lambda n: (n + 15) // 16 * 16  # noqa: E731
+        items, t_max, w_max = len(frames), features.shape[2], targets.shape[2]
+        pieces = np.array(
+            [(i * t_max, frames[i], plan.frame_off[i], align(frames[i]))
+             for i in range(items)] +
+            [(i * w_max, words[i], plan.word_off[i], align(words[i]))
+             for i in range(items)], dtype=np.int64)
+        with torch.cuda.device(self.device):
+            device_meta = torch.from_numpy(host).to(self.device)
+            meta = {name: device_meta[start:start + size]
+                    for name, (start, size) in offsets.items()}
+            meta['_buffer'] = device_meta
+            table = torch.from_numpy(pieces).to(self.device)
+            source = features.to(self.device, torch.float32).permute(
+                1, 0, 2).reshape(config.num_features, items * t_max).contiguous()
+            packed = torch.zeros(
+                (config.num_features, plan.ld_frames), dtype=torch.float32,
+                device=self.device)
+            runtime.check(self.lib.emph_gather_columns(
+                source.data_ptr(), source.shape[1], packed.data_ptr(),
+                plan.ld_frames, config.num_features, table.data_ptr(), items,
+                runtime.stream()), 'emph_gather_columns')
+            source = targets.to(self.device, torch.float32).reshape(
+                1, items * w_max).contiguous()
+            packed_targets = torch.zeros(
+                plan.ld_words, dtype=torch.float32, device=self.device)
+            runtime.check(self.lib.emph_gather_columns(
+                source.data_ptr(), source.shape[1], packed_targets.data_ptr(),
+                plan.ld_words, 1, table[items:].data_ptr(), items,
+                runtime.stream()), 'emph_gather_columns')
+        return Batch(plan, meta, packed, packed_targets)
+
+    def _batch(self, arguments):
+        if len(arguments) == 1 and isinstance(arguments[0], Batch):
+            return arguments[0]
+        return self.prepare(*arguments)
+
+    def _buffers(self, plan):
+        """The activations and gradients of a step for a packed layout, kept
+        between steps (zero at first, so that padding columns stay finite)."""
+        frame_tiles = len(plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
+        word_tiles = len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE))
+        parts = max(
+            int(self.lib.emph_conv_weight_grad_parts(n))
+            for n in (frame_tiles, word_tiles))
+        key = (plan.ld_frames, plan.ld_words, parts)
+        found = self._workspace.get(key)
+        if found is None:
+            self._workspace.clear()
+            channels, layers = self.config.channels, self.config.layers
+            zeros = lambda *shape: torch.zeros(  # noqa: E731
+                shape, dtype=torch.float32, device=self.device)
+            slab = channels * 3 * self.config.num_features + channels
+            found = {
+                'frames': zeros(layers + 1, channels, plan.ld_frames),
+                'words': zeros(layers + 1, channels, plan.ld_words),
+                'frame_grad': zeros(2, channels, plan.ld_frames),
+                'word_grad': zeros(2, channels, plan.ld_words),
+                'logits': zeros(plan.ld_words),
+                'dlogit': zeros(plan.ld_words),
+                'slabs': zeros(max(parts, 1) * slab)}
+            self._workspace[key] = found
+        return found
+
+    ###########################################################################
+    # Launches
+    ###########################################################################
+
+    def _repack(self):
+        runtime.check(self.lib.emph_take(
+            self.parameters.data_ptr(), self.take_index.data_ptr(),
+            self.packs.data_ptr(), self.packs.numel(), runtime.stream()),
+            'emph_take')
+
+    def _parameter(self, name):
+        return self.parameters.data_ptr() + 4 * self.offsets[name][0]
+
+    def _gradient(self, name):
+        return self.gradients.data_ptr() + 4 * self.offsets[name][0]
+
+    def _conv(self, pack, bias, x, y, ld, c_in, activation, tiles, tile):
+        runtime.check(self.lib.emph_conv1d(
+            x.data_ptr(), ld, y.data_ptr(), ld,
+            self.packs.data_ptr() + 4 * pack[0], bias, c_in,
+            self.config.channels, 3, runtime.ACTIVATIONS[activation],
+            tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS, tile, 0,
+            runtime.stream()), 'emph_conv1d')
+
+    def _forward_backward(self, batch):
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_f, ld_w = plan.ld_frames, plan.ld_words
+        frames, words = runtime.AXIS_FRAMES, runtime.AXIS_WORDS
+        buffers = self._buffers(plan)
+        stream = runtime.stream()
+        frame_tiles = meta[('tiles', frames, FRAME_TILE)]
+        word_tiles = meta[('tiles', words, WORD_TILE)]
+        word_grad_tiles = meta[('tiles', words, GRAD_TILE)]
+        table, bounds = meta['table'], meta['bounds']
+        word_segment = meta['word_segment']
+        mode = runtime.REDUCTIONS[config.downsample_method]
+        encoder = [f'frame_encoder.{2 * i}' for i in range(layers)]
+        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
+
+        # ---- forward, every layer's output kept (model/core.py:91-107,138)
+        h, d = buffers['frames'], buffers['words']
+        self._conv(self._forward_packs['input_layer'],
+                   self._parameter('input_layer.bias'), batch.features, h[0],
+                   ld_f, config.num_features, None, frame_tiles, FRAME_TILE)
+        for i, name in enumerate(encoder):
+            self._conv(self._forward_packs[name],
+                       self._parameter(f'{name}.bias'), h[i], h[i + 1], ld_f,
+                       channels, 'relu', frame_tiles, FRAME_TILE)
+        runtime.check(lib.emph_segment_reduce(
+            h[layers].data_ptr(), ld_f, bounds.data_ptr(), d[0].data_ptr(),
+            ld_w, channels, table.data_ptr(), word_segment.data_ptr(), ld_w,
+            mode, stream), 'emph_segment_reduce')
+        for i, name in enumerate(decoder):
+            self._conv(self._forward_packs[name],
+                       self._parameter(f'{name}.bias'), d[i], d[i + 1], ld_w,
+                       channels, 'relu', word_tiles, WORD_TILE)
+        logits, dlogit = buffers['logits'], buffers['dlogit']
+        runtime.check(lib.emph_output_layer(
+            d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
+            self._parameter('output_layer.bias'), channels, 3,
+            table.data_ptr(), word_segment.data_ptr(), ld_w, words, 0,
+            logits.data_ptr(), None, stream), 'emph_output_layer')
+
+        # ---- loss (train/core.py:315-353) and backward
+        runtime.check(lib.emph_loss_grad(
+            logits.data_ptr(), batch.targets.data_ptr(),
+            word_segment.data_ptr(), ld_w, plan.total_words,
+            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
+            dlogit.data_ptr(), stream), 'emph_loss_grad')
+        dd, dh = buffers['word_grad'], buffers['frame_grad']
+        runtime.check(lib.emph_output_layer_backward(
+            dlogit.data_ptr(), d[layers].data_ptr(), ld_w,
+            self._parameter('output_layer.weight'), word_segment.data_ptr(),
+            channels, 3, ld_w, self._gradient('output_layer.weight'),
+            self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
+            stream), 'emph_output_layer_backward')
+
+        def backward(names, outputs, gradient, ld, grad_tiles, tiles, tile):
+            """From the gradient of the last output (gradient[0]) down to the
+            gradient of outputs[0]; returns the buffer that holds it."""
+            current = 0
+            for i in range(len(names) - 1, -1, -1):
+                name = names[i]
+                dy = gradient[current]
+                runtime.check(lib.emph_activation_backward(
+                    outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
+                    runtime.ACTIVATIONS['relu'], stream),
+                    'emph_activation_backward')
+                self._weight_grad(dy, outputs[i], ld, channels, name,
+                                  grad_tiles, buffers)
+                self._conv(self._backward_packs[name], None, dy,
+                           gradient[1 - current], ld, channels, None, tiles,
+                           tile)
+                current = 1 - current
+            return gradient[current]
+
+        dword = backward(decoder, d, dd, ld_w, word_grad_tiles, word_tiles,
+                         WORD_TILE)
+        runtime.check(lib.emph_segment_broadcast(
+            dword.data_ptr(), ld_w, bounds.data_ptr(), dh[0].data_ptr(), ld_f,
+            channels, table.data_ptr(), frame_tiles.data_ptr(),
+            frame_tiles.numel() // runtime.TILE_FIELDS, mode, stream),
+            'emph_segment_broadcast')
+        dinput = backward(encoder, h, dh, ld_f, frame_tiles, frame_tiles,
+                          FRAME_TILE)
+        self._weight_grad(dinput, batch.features, ld_f, config.num_features,
+                          'input_layer', frame_tiles, buffers)
+
+    def _weight_grad(self, dy, x, ld, c_in, name, tiles, buffers):
+        runtime.check(self.lib.emph_conv_weight_grad(
+            dy.data_ptr(), ld, x.data_ptr(), ld, c_in, self.config.channels, 3,
+            tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS, GRAD_TILE,
+            buffers['slabs'].data_ptr(), self._gradient(f'{name}.weight'),
+            self._gradient(f'{name}.bias'), runtime.stream()),
+            'emph_conv_weight_grad')
+
+    ###########################################################################
+    # API
+    ###########################################################################
+
+    def loss_and_gradients(self, *batch):
+        """(loss, {name: gradient}) of a collated batch (or a prepared
+        `Batch`), device tensors; the parameters are left as they are."""
+        batch = self._batch(batch)
+        with torch.cuda.device(self.device):
+            self._forward_backward(batch)
+            flat = self.gradients.clone()
+            loss = self.loss[0].clone()
+        return loss, collections.OrderedDict(
+            (name, self._view(flat, name)) for name in self.offsets)
+
+    def step(self, *batch):
+        """Forward, loss, backward, Adam and the next step's packs on the
+        current stream; returns the loss (before the update) as a 0-dim device
+        tensor without synchronising."""
+        batch = self._batch(batch)
+        with torch.cuda.device(self.device):
+            self._forward_backward(batch)
+            loss = self.loss[0].clone()
+            self.steps += 1
+            beta1, beta2 = self.betas
+            correction1 = 1. - beta1 ** self.steps
+            correction2 = 1. - beta2 ** self.steps
+            runtime.check(self.lib.emph_adam_step(
+                self.parameters.data_ptr(), self.gradients.data_ptr(),
+                self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.count, beta1, beta2, self.lr / correction1,
+                math.sqrt(correction2), self.eps, runtime.stream()),
+                'emph_adam_step')
+            self._repack()
+        return loss

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 33
+#define EMPH_ABI_VERSION 34
 
 /* Segment-table fields */
 enum {
@@ -1057,6 +1057,91 @@ int emph_prominence_forward(const emph_conv_model* model, const void* audio,
                             const emph_word_sum_tables* word_sums,
                             const int32_t* conv_spans, int32_t n_conv_spans,
                             void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* Training step of the convolution model                                    */
+/* ------------------------------------------------------------------------ */
+
+/* The reference trains with autograd and torch.optim.Adam
+ * (emphases/train/core.py:111-142).  These entry points are one step of that
+ * loop for the convolution model in fp32 (no autocast, no GradScaler), every
+ * utterance with its own zero halo.  Nothing here uses floating-point atomics
+ * or a hand-off between workgroups: the same inputs give the same bits.  The
+ * forward pass is emph_conv1d / emph_segment_reduce / emph_output_layer with
+ * every layer's output kept; the data gradient of a Conv1d(80, 80, 3) is
+ * emph_conv1d itself (EMPH_ACT_NONE, no bias) on the pack of
+ * W'[ci][co][j] = W[co][ci][2 - j]. */
+
+/* out[i] = index[i] < 0 ? 0 : src[index[i]], i < count.  With a table made
+ * once on the host (emph_conv_pack of an arange) one launch rebuilds every
+ * MFMA weight pack from the flat parameter buffer after an optimizer step;
+ * the reference's modules read their parameters in place
+ * (model/layers/convolution.py:25-28). */
+int emph_take(const float* src, const int32_t* index, float* out, int64_t count,
+              void* stream);
+
+/* Masked loss and its gradient (emphases/train/core.py:315-353):
+ * `logits`, `targets` and `dlogit` are [columns] on the packed word axis,
+ * word_segment[column] < 0 marks padding, `valid_words` = N is the number of
+ * the others.  form 0: mean of binary_cross_entropy_with_logits,
+ * max(z,0) - z y + log1p(exp(-|z|)), dlogit = (sigmoid(z) - y) / N; form 1:
+ * mean of (z - y)^2, dlogit = 2 (z - y) / N.  dlogit = 0 on padding.  One
+ * workgroup, fixed-order sum of the loss in double, rounded to float once;
+ * loss[0] is written on the device. */
+int emph_loss_grad(const float* logits, const float* targets,
+                   const int32_t* word_segment, int64_t columns, int64_t valid_words,
+                   int32_t form, float* loss, float* dlogit, void* stream);
+
+/* Backward of the output projection Conv1d(channels, 1, 3, 'same')
+ * (emphases/model/core.py:33-37,138), inside every segment:
+ *   dweight[c][j] = sum_w dlogit[w] x[c][w + j - 1]    dbias[0] = sum_w dlogit[w]
+ *   dx[c][w] = sum_j weight[c][j] dlogit[w - j + 1]    (0 on padding columns) */
+int emph_output_layer_backward(const float* dlogit, const float* x, int64_t ldx,
+                               const float* weight, const int32_t* word_segment,
+                               int32_t channels, int32_t kernel_size, int64_t columns,
+                               float* dweight, float* dbias, float* dx, int64_t ld_dx,
+                               void* stream);
+
+/* Backward of the activation of model/layers/convolution.py:28, in place:
+ * gradient[i] = y[i] > 0 ? gradient[i] : 0 from the saved output y
+ * (EMPH_ACT_RELU only).  count a multiple of 4, pointers 16-byte aligned. */
+int emph_activation_backward(const float* y, float* gradient, int64_t count,
+                             int32_t activation, void* stream);
+
+/* Backward of emph_segment_reduce (emphases.downsample, core.py:426-469) for
+ * EMPH_REDUCE_SUM / EMPH_REDUCE_AVERAGE: dx[c][t] = dword[c][w(t)] (divided by
+ * end - start for the average) for a frame t inside word w(t), 0 elsewhere.
+ * The words of a segment must be sorted and must not overlap.  `tiles`: the
+ * 64-wide tile table of the frame axis; `bounds` as emph_segment_reduce. */
+int emph_segment_broadcast(const float* dword, int64_t ldw, const int32_t* bounds,
+                           float* dx, int64_t ldx, int32_t channels, const int64_t* seg,
+                           const int32_t* tiles, int32_t n_tiles, int32_t mode,
+                           void* stream);
+
+/* Weight and bias gradient of Conv1d(c_in, 80, 3, 'same')
+ * (model/core.py:17-21, model/layers/convolution.py:25-28 under autograd):
+ *   dweight[co][ci][j] = sum_t dy[co][t] x[ci][t + j - 1]   dbias[co] = sum_t dy[co][t]
+ * inside every segment of the 64-wide tile table `tiles`, x zero outside its
+ * segment; c_in in 1..96, either axis.  Two launches: the first writes
+ * emph_conv_weight_grad_parts(n_tiles) slabs of 80 (3 c_in) + 80 floats into
+ * `workspace`, the second adds them in a fixed order that depends on their
+ * number alone (no atomics: the same inputs give the same bits). */
+int32_t emph_conv_weight_grad_parts(int32_t n_tiles);
+int emph_conv_weight_grad(const float* dy, int64_t ld_dy, const float* x, int64_t ldx,
+                          int32_t c_in, int32_t c_out, int32_t kernel_size,
+                          const int32_t* tiles, int32_t n_tiles, int32_t tile_n,
+                          float* workspace, float* dweight, float* dbias, void* stream);
+
+/* torch.optim.Adam's single-tensor update (train/core.py:40,139) over flat
+ * buffers of `count` floats:
+ *   m += (1 - beta1) (g - m)    v = beta2 v + (1 - beta2) g g
+ *   p -= step_size m / (sqrt(v) / correction2_sqrt + eps)
+ * step_size = lr / (1 - beta1^t), correction2_sqrt = sqrt(1 - beta2^t), both
+ * formed by the caller in float64; 1 - beta1 and 1 - beta2 are formed here in
+ * float64 and rounded once, as torch's Python scalars are. */
+int emph_adam_step(float* parameter, const float* gradient, float* exp_avg,
+                   float* exp_avg_sq, int64_t count, double beta1, double beta2,
+                   float step_size, float correction2_sqrt, float eps, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Measurement                                                               */

@@ -1,0 +1,183 @@
+"""One training step at the reference's training size, against PyTorch.
+
+    python tools/train_bench.py [--laps 7] [--seconds 1.0] [--out profiles/train_step.json]
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --steps 20
+
+The batch is what the reference's sampler fills up to (`MAX_TRAINING_FRAMES =
+75 000`, `config/defaults.py`): 75 utterances x 1 000 frames x 30 words,
+default configuration, weights of `emphases.Model()` under seed 0.
+
+Three contenders run in ALTERNATING laps of the same process on the same GPU:
+
+  ours            `emphases_amd.train.Trainer.step` on a prepared batch
+  torch_fp32      the same model as torch.nn.Conv1d + ReLU modules, the word
+                  sums as one batched matmul with a 0/1 frame-to-word matrix
+                  (the reference's per-word Python loop would only measure the
+                  interpreter), `binary_cross_entropy_with_logits`, autograd,
+                  `torch.optim.Adam` - in float32
+  torch_autocast  the same under `torch.autocast` + `GradScaler`, as the
+                  reference trains (`train/core.py:78,111,136-142`)
+
+Every utterance has the same lengths, so the padded batch of the torch model
+and the ragged batch of this package compute the same function.  A lap of one
+contender is timed with a pair of device events around `steps` steps, `steps`
+chosen so that a lap takes about `--seconds`; both sides are warmed up first.
+Reported: median, minimum and maximum per-step time over the laps.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import emphases_amd  # noqa: E402
+from emphases_amd import train  # noqa: E402
+
+ITEMS, FRAMES, WORDS = 75, 1000, 30
+PEAK_FP32_MATRIX = 157.3e12
+
+
+def make_batch(seed=0):
+    rng = np.random.default_rng(seed)
+    features = torch.from_numpy(
+        rng.standard_normal((ITEMS, 80, FRAMES)).astype(np.float32))
+    bounds = torch.zeros(ITEMS, 2, WORDS, dtype=torch.long)
+    for item in range(ITEMS):
+        cuts = np.sort(rng.choice(
+            np.arange(1, FRAMES), size=WORDS - 1, replace=False))
+        edges = np.concatenate([[0], cuts, [FRAMES]])
+        bounds[item, 0] = torch.from_numpy(edges[:-1])
+        bounds[item, 1] = torch.from_numpy(edges[1:])
+    targets = torch.from_numpy(
+        rng.uniform(0., 1., (ITEMS, 1, WORDS)).astype(np.float32))
+    return (features, torch.full((ITEMS,), FRAMES), bounds,
+            torch.full((ITEMS,), WORDS), targets)
+
+
+class TorchModel(torch.nn.Module):
+    """`emphases.Model` of the default configuration (`model/core.py`)."""
+
+    def __init__(self, state):
+        super().__init__()
+        conv = lambda c_in, c_out: torch.nn.Conv1d(  # noqa: E731
+            c_in, c_out, kernel_size=3, padding='same')
+        stack = lambda: torch.nn.Sequential(*[  # noqa: E731
+            module for _ in range(6)
+            for module in (conv(80, 80), torch.nn.ReLU())])
+        self.input_layer = conv(80, 80)
+        self.frame_encoder = stack()
+        self.word_decoder = stack()
+        self.output_layer = conv(80, 1)
+        self.load_state_dict(
+            {name: torch.from_numpy(value) for name, value in state.items()})
+
+    def forward(self, features, membership):
+        frames = self.frame_encoder(self.input_layer(features))
+        words = torch.bmm(frames, membership.to(frames.dtype))
+        return self.output_layer(self.word_decoder(words))
+
+
+def torch_step(model, optimizer, scaler, features, membership, targets):
+    with torch.autocast('cuda', enabled=scaler is not None):
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(
+            model(features, membership), targets)
+    optimizer.zero_grad()
+    if scaler is None:
+        loss.backward()
+        optimizer.step()
+    else:
+        scaler.scale(loss).backward()
+        scaler.step(optimizer)
+        scaler.update()
+    return loss
+
+
+def timed(function, steps):
+    begin = torch.cuda.Event(enable_timing=True)
+    end = torch.cuda.Event(enable_timing=True)
+    begin.record()
+    for _ in range(steps):
+        function()
+    end.record()
+    end.synchronize()
+    return begin.elapsed_time(end) / steps
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--laps', type=int, default=7)
+    parser.add_argument('--seconds', type=float, default=1.0)
+    parser.add_argument('--steps', type=int, default=None)
+    parser.add_argument('--only', choices=('ours',), default=None)
+    parser.add_argument('--out', default=None)
+    arguments = parser.parse_args()
+    torch.cuda.set_device(0)
+    batch = make_batch()
+    state = train.initial_state(emphases_amd.DEFAULT, seed=0)
+    ours = train.Trainer(checkpoint=state, gpu=0)
+    prepared = ours.prepare(*batch)
+    contenders = {'ours': lambda: ours.step(prepared)}
+    if arguments.only is None:
+        features, _, bounds, _, targets = (item.cuda() for item in batch)
+        frame = torch.arange(FRAMES, device='cuda')[None, :, None]
+        membership = ((frame >= bounds[:, 0, None, :]) &
+                      (frame < bounds[:, 1, None, :])).float()
+        for name, mixed in (('torch_fp32', False), ('torch_autocast', True)):
+            model = TorchModel(state).cuda()
+            optimizer = torch.optim.Adam(model.parameters())
+            scaler = torch.amp.GradScaler('cuda') if mixed else None
+            contenders[name] = (
+                lambda m=model, o=optimizer, s=scaler: torch_step(
+                    m, o, s, features, membership, targets))
+    first = {}
+    for name, function in contenders.items():
+        first[name] = float(function())
+        for _ in range(4):
+            function()
+    torch.cuda.synchronize()
+    steps = {}
+    for name, function in contenders.items():
+        probe = timed(function, 5)
+        steps[name] = arguments.steps or max(
+            5, int(arguments.seconds * 1e3 / probe))
+    if arguments.only:
+        timed(contenders['ours'], steps['ours'])
+        print(json.dumps({'ours_steps': steps['ours']}))
+        return
+    laps = {name: [] for name in contenders}
+    for _ in range(arguments.laps):
+        for name, function in contenders.items():
+            laps[name].append(timed(function, steps[name]))
+    record = {
+        'batch': {'utterances': ITEMS, 'frames': FRAMES, 'words': WORDS},
+        'device': torch.cuda.get_device_name(0),
+        'laps': arguments.laps, 'steps_per_lap': steps,
+        'first_loss': first,
+        'ms_per_step': {
+            name: {'median': float(np.median(values)),
+                   'min': float(np.min(values)), 'max': float(np.max(values))}
+            for name, values in laps.items()}}
+    median = {name: record['ms_per_step'][name]['median'] for name in laps}
+    record['torch_fp32_over_ours'] = median['torch_fp32'] / median['ours']
+    record['torch_autocast_over_ours'] = \
+        median['torch_autocast'] / median['ours']
+    # executed MFMA flops of emph_conv_weight_grad per step: 64-position
+    # tiles, 5 m-tiles x (3 x 5 + 1) n-tiles of 16 x 16 per k-step of 4
+    tiles = ITEMS * -(-FRAMES // 64), ITEMS * -(-WORDS // 64)
+    record['weight_grad_executed_flops'] = float(
+        2 * 16 * 16 * 64 * 5 * 16 * (7 * tiles[0] + 6 * tiles[1]))
+    record['fp32_matrix_peak_flops'] = PEAK_FP32_MATRIX
+    print(json.dumps(record))
+    if arguments.out:
+        with open(arguments.out, 'w') as file:
+            json.dump(record, file, indent=1)
+            file.write('\n')
+
+
+if __name__ == '__main__':
+    main()
