@@ -1,6 +1,9 @@
-"""`emphases.data` of the reference, as far as the inference hot path reaches:
-`emphases.data.preprocess` (`/root/reference/emphases/data/__init__.py`).
-The feature cache of whole datasets is written by `preprocess.datasets`;
-loaders, samplers, partitions and downloads belong to training and are out of
-scope."""
+"""`emphases.data` of the reference: `emphases.data.preprocess` writes the
+feature cache of whole datasets (`preprocess.datasets`); `Dataset`, `Sampler`
+and `Loader` read it back for training, resident on the device (partitions
+and downloads stay out of scope)."""
 from . import preprocess  # noqa: F401
+from .collate import collate  # noqa: F401
+from .dataset import Dataset  # noqa: F401
+from .loader import Loader  # noqa: F401
+from .sampler import Sampler  # noqa: F401

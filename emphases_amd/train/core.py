@@ -345,10 +345,7 @@ class Trainer:
             features, frame_lengths, word_bounds, word_lengths, targets,
             config)
         plan = api._packed_plan(frames, torch.from_numpy(bounds), words)
-        requests = [(runtime.AXIS_FRAMES, FRAME_TILE),
-                    (runtime.AXIS_WORDS, WORD_TILE),
-                    (runtime.AXIS_WORDS, GRAD_TILE)]
-        host, offsets = plan.pack_metadata(list(dict.fromkeys(requests)))
+        meta = self.metadata(plan)
         # emph_gather_columns pieces: (source column, length, target column,
         # columns to write; the rest zero) of every item, frames then words
         align = lambda n: (n + 15) // 16 * 16  # noqa: E731
@@ -359,10 +356,6 @@ class Trainer:
             [(i * w_max, words[i], plan.word_off[i], align(words[i]))
              for i in range(items)], dtype=np.int64)
         with torch.cuda.device(self.device):
-            device_meta = torch.from_numpy(host).to(self.device)
-            meta = {name: device_meta[start:start + size]
-                    for name, (start, size) in offsets.items()}
-            meta['_buffer'] = device_meta
             table = torch.from_numpy(pieces).to(self.device)
             source = features.to(self.device, torch.float32).permute(
                 1, 0, 2).reshape(config.num_features, items * t_max).contiguous()
@@ -382,6 +375,20 @@ class Trainer:
                 plan.ld_words, 1, table[items:].data_ptr(), items,
                 runtime.stream()), 'emph_gather_columns')
         return Batch(plan, meta, packed, packed_targets)
+
+    def metadata(self, plan):
+        """The integer tables of a step for a packed layout on the device: one
+        copy, views by name (`Batch.meta`)."""
+        requests = [(runtime.AXIS_FRAMES, FRAME_TILE),
+                    (runtime.AXIS_WORDS, WORD_TILE),
+                    (runtime.AXIS_WORDS, GRAD_TILE)]
+        host, offsets = plan.pack_metadata(list(dict.fromkeys(requests)))
+        with torch.cuda.device(self.device):
+            device_meta = torch.from_numpy(host).to(self.device)
+        meta = {name: device_meta[start:start + size]
+                for name, (start, size) in offsets.items()}
+        meta['_buffer'] = device_meta
+        return meta
 
     def _batch(self, arguments):
         if len(arguments) == 1 and isinstance(arguments[0], Batch):
@@ -439,7 +446,9 @@ class Trainer:
             tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS, tile, 0,
             runtime.stream()), 'emph_conv1d')
 
-    def _forward_backward(self, batch):
+    def _forward(self, batch):
+        """The forward launches of a step; returns the step's buffers, whose
+        'logits' then hold the packed logits [ld_words]."""
         config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
         channels, layers = config.channels, config.layers
         ld_f, ld_w = plan.ld_frames, plan.ld_words
@@ -448,7 +457,6 @@ class Trainer:
         stream = runtime.stream()
         frame_tiles = meta[('tiles', frames, FRAME_TILE)]
         word_tiles = meta[('tiles', words, WORD_TILE)]
-        word_grad_tiles = meta[('tiles', words, GRAD_TILE)]
         table, bounds = meta['table'], meta['bounds']
         word_segment = meta['word_segment']
         mode = runtime.REDUCTIONS[config.downsample_method]
@@ -472,12 +480,30 @@ class Trainer:
             self._conv(self._forward_packs[name],
                        self._parameter(f'{name}.bias'), d[i], d[i + 1], ld_w,
                        channels, 'relu', word_tiles, WORD_TILE)
-        logits, dlogit = buffers['logits'], buffers['dlogit']
+        logits = buffers['logits']
         runtime.check(lib.emph_output_layer(
             d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
             self._parameter('output_layer.bias'), channels, 3,
             table.data_ptr(), word_segment.data_ptr(), ld_w, words, 0,
             logits.data_ptr(), None, stream), 'emph_output_layer')
+        return buffers
+
+    def _forward_backward(self, batch):
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_f, ld_w = plan.ld_frames, plan.ld_words
+        buffers = self._forward(batch)
+        stream = runtime.stream()
+        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
+        word_grad_tiles = meta[('tiles', runtime.AXIS_WORDS, GRAD_TILE)]
+        table, bounds = meta['table'], meta['bounds']
+        word_segment = meta['word_segment']
+        mode = runtime.REDUCTIONS[config.downsample_method]
+        encoder = [f'frame_encoder.{2 * i}' for i in range(layers)]
+        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
+        h, d = buffers['frames'], buffers['words']
+        logits, dlogit = buffers['logits'], buffers['dlogit']
 
         # ---- loss (train/core.py:315-353) and backward
         runtime.check(lib.emph_loss_grad(
@@ -535,6 +561,16 @@ class Trainer:
     ###########################################################################
     # API
     ###########################################################################
+
+    def logits(self, batch):
+        """The model's logits of a prepared `Batch`: the forward launches of a
+        step alone (no loss, no gradient, no update).  Compact float32
+        [total_words] on the device, the words of the items in order."""
+        with torch.cuda.device(self.device):
+            packed = self._forward(batch)['logits']
+            columns = torch.from_numpy(
+                batch.plan.word_columns()).to(self.device)
+            return packed[columns]
 
     def loss_and_gradients(self, *batch):
         """(loss, {name: gradient}) of a collated batch (or a prepared

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 34
+#define EMPH_ABI_VERSION 35
 
 /* Segment-table fields */
 enum {
@@ -555,6 +555,30 @@ int emph_output_layer(const float* x, int64_t ldx, const float* weight,
 int emph_gather_columns(const float* x, int64_t ldx, float* y, int64_t ldy,
                         int32_t channels, const int64_t* pieces,
                         int32_t n_pieces, void* stream);
+
+/* A packed training batch out of a device-resident dataset, one launch (the
+ * host collate of emphases/data/collate.py:11-78 plus the upload and the two
+ * emph_gather_columns launches that followed it).
+ *   features  [channels][ld_cache]: every utterance's frames, back to back
+ *   targets   [total_words]: every utterance's word targets, back to back
+ *   items     int64 [n_items][6] on the DEVICE = (first column of the item in
+ *             `features`, frames, its first column in `out_features`, its first
+ *             word in `targets`, words, its first column in `out_targets`),
+ *             rising along both packed axes (a plan's frame_off / word_off)
+ * EVERY column 0 .. ld_frames of every row of out_features [channels]
+ * [ld_frames] and 0 .. ld_words of out_targets is written: the items' data
+ * where the table puts it (bitwise the source), zero everywhere else, so the
+ * outputs need no memset and may hold anything before.  ld_frames and ld_words
+ * are multiples of 4 and the outputs 16-byte aligned.  Quads that lie inside
+ * one item and whose source is 16-byte aligned (utterances stored on multiples
+ * of 4 columns) move as 16-byte loads and stores, the others column by column.
+ * The table is device memory: an item that does not lie inside its source
+ * (negative, or past ld_cache / total_words) is written as zeros; the caller
+ * vouches that the items do not overlap in the outputs. */
+int emph_collate(const float* features, int64_t ld_cache, const float* targets,
+                 int64_t total_words, const int64_t* items, int32_t n_items,
+                 int32_t channels, int64_t ld_frames, int64_t ld_words,
+                 float* out_features, float* out_targets, void* stream);
 
 /* The packed feature matrix of a batch (emph_logmel: x [rows][ld], segments on
  * multiples of 16 columns) taken apart into the C-contiguous tensors a feature
