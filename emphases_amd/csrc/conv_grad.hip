@@ -25,15 +25,13 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "conv_grad.h"
 
 namespace emph {
 
 typedef float grad_f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kGradTile = 64;            // positions per staged tile
 constexpr int kGradStride = 68;          // floats per LDS row (66 used)
-constexpr int kGradOut = 80;             // output channels (5 m-tiles)
-constexpr int kGradParts = 256;          // at most one slab per CU
 
 __host__ __device__ constexpr int grad_wave_tiles(int ct) { return (3 * ct + 1 + 3) / 4; }
 
@@ -195,8 +193,12 @@ __global__ __launch_bounds__(256) void conv_weight_grad_sum_kernel(
     if (i < weight_count) dweight[i] = sum; else dbias[i - weight_count] = sum;
 }
 
-static int grad_tiles_per_part(int n_tiles) {
-    return (n_tiles + kGradParts - 1) / kGradParts;
+int conv_weight_grad_sum(const float* slabs, int parts, int64_t weight_count, float* dweight,
+                         float* dbias, hipStream_t stream, const char* what) {
+    const int64_t total = weight_count + kGradOut;
+    EMPH_LAUNCH(conv_weight_grad_sum_kernel, dim3(static_cast<unsigned>((total + 63) / 64)),
+                dim3(256), 0, stream, slabs, parts, weight_count, dweight, dbias);
+    return check_launch(what);
 }
 
 }  // namespace emph
@@ -239,11 +241,8 @@ int emph_conv_weight_grad(const float* dy, int64_t ld_dy, const float* x, int64_
                     ldx, c_in, tiles, n_tiles, per_part, workspace);
     }
     if (int status = check_launch("emph_conv_weight_grad")) return status;
-    const int64_t weight_count = static_cast<int64_t>(kGradOut) * c_in * 3;
-    const int64_t total = weight_count + kGradOut;
-    EMPH_LAUNCH(conv_weight_grad_sum_kernel, dim3(static_cast<unsigned>((total + 63) / 64)),
-                dim3(256), 0, s, workspace, parts, weight_count, dweight, dbias);
-    return check_launch("emph_conv_weight_grad");
+    return conv_weight_grad_sum(workspace, parts, static_cast<int64_t>(kGradOut) * c_in * 3,
+                                dweight, dbias, s, "emph_conv_weight_grad");
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -209,6 +209,10 @@ SIGNATURES = {
     'emph_conv_weight_grad': (_c.c_int, [
         _ptr, _i64, _ptr, _i64, _i32, _i32, _i32, _ptr, _i32, _i32, _ptr,
         _ptr, _ptr, _ptr]),
+    'emph_conv_weight_grad_split': (_c.c_int, [
+        _ptr, _i64, _ptr, _i64, _i32, _i32, _i32, _ptr, _i32, _i32, _ptr,
+        _ptr, _ptr, _ptr]),
+    'emph_conv_split_pack_device': (_c.c_int, [_ptr, _ptr, _ptr, _i32, _ptr]),
     'emph_adam_step': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _i64, _c.c_double, _c.c_double, _f32, _f32,
         _f32, _ptr]),

@@ -42,11 +42,15 @@ def parse_args(arguments=None):
     parser.add_argument(
         '--downsample_method', choices=('sum', 'average'),
         help="The word reduction: 'sum' (default) or 'average'")
+    parser.add_argument(
+        '--precision', choices=emphases_amd.train.PRECISIONS, default='f32',
+        help="'f32' (default), or 'bf16x3': the frame-rate convolutions of "
+             'the step on the bf16 matrix pipe, two pieces per operand')
     return parser.parse_args(arguments)
 
 
-def main():
-    arguments = vars(parse_args())
+def main(arguments=None):
+    arguments = vars(parse_args(arguments))
     overrides = {
         name: arguments.pop(name) for name in ('loss', 'downsample_method')}
     overrides = {

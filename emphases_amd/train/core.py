@@ -4,8 +4,15 @@ What the reference does per batch (`emphases/train/core.py:105-142`: forward
 in train mode, `loss`, `backward`, `optimizer.step`) as launches of the HIP
 library on one stream.  Deliberate, documented deviations:
 
-* float32 throughout: no `torch.autocast`, no `GradScaler`
-  (`train/core.py:78,111,136-142`) - as inference (`core.inference_context`);
+* no `torch.autocast`, no `GradScaler` (`train/core.py:78,111,136-142`):
+  float32 throughout by default, as inference (`core.inference_context`).
+  `precision='bf16x3'` is the mixed precision of this package instead: the
+  Conv1d(80, 80, 3) layers on the frame axis - forward, data gradient and
+  weight gradient - multiply on the bf16 matrix pipe with every float32
+  operand split into two bf16 pieces (three products per term, float32
+  accumulation: `emph_conv1d_split`, `emph_conv_weight_grad_split`), while
+  the word-rate layers, the output layer, the loss and Adam stay float32, as
+  do the parameters, the gradients and the moments;
 * every utterance is trained alone, with its own zero halo, exactly as
   inference runs it; the reference's padded batch leaks bias + ReLU of the
   padding into the last frames and words of every shorter utterance
@@ -17,7 +24,9 @@ order (the order of `Model.parameters()`); gradients and the two Adam moments
 are buffers of the same shape.  The MFMA weight packs of the forward kernel
 (`emph_conv1d`) and of the data gradient (the same kernel on
 W'[ci][co][j] = W[co][ci][2 - j]) are rebuilt after every update by ONE
-gather launch (`emph_take`) through a table made once on the host.
+gather launch (`emph_take`) through a table made once on the host; under
+'bf16x3' one more launch (`emph_conv_split_pack_device`) splits the weights
+of the layers in scope into the packs of `emph_conv1d_split`, both ways.
 """
 import collections
 import math
@@ -34,6 +43,8 @@ from .. import weights as weights_module
 FRAME_TILE = 64      # emph_conv1d, emph_conv_weight_grad, emph_segment_broadcast
 WORD_TILE = 32       # emph_conv1d on the word axis
 GRAD_TILE = 64       # emph_conv_weight_grad on either axis
+PRECISIONS = ('f32', 'bf16x3')
+SPLIT_CHANNELS = 80  # emph_conv1d_split, emph_conv_weight_grad_split
 
 
 def check_supported(config):
@@ -65,6 +76,33 @@ def check_supported(config):
         refuse('layers', '0..16')
     if not config.mel_feature:
         refuse('mel_feature', 'True (80..83 input features)')
+
+
+def check_precision(precision):
+    """'f32' or 'bf16x3'; NotImplementedError for the inference precisions the
+    step does not cover, ValueError for anything else - before a GPU is
+    needed."""
+    from .. import engine
+    if not isinstance(precision, str):
+        raise ValueError(
+            f'precision must be one of {sorted(engine.PRECISIONS)}, not '
+            f'{precision!r}')
+    if precision in PRECISIONS:
+        return precision
+    if precision in engine.PRECISIONS:
+        raise NotImplementedError(
+            f'the training step supports precision {PRECISIONS} only, not '
+            f'precision={precision!r}')
+    raise ValueError(
+        f'precision {precision!r} is not one of {sorted(engine.PRECISIONS)}')
+
+
+def split_layer_names(config):
+    """The layers of `layer_names` that run on the bf16 pipe under
+    precision='bf16x3': the Conv1d(80, 80, 3) on the frame axis (the input
+    layer only when it has exactly 80 feature rows)."""
+    names = ['input_layer'] if config.num_features == SPLIT_CHANNELS else []
+    return names + [f'frame_encoder.{2 * i}' for i in range(config.layers)]
 
 
 def layer_names(config):
@@ -147,6 +185,42 @@ def gather_tables(config=cfg.DEFAULT):
             pieces.append(piece)
             cursor += piece.size
     index = np.concatenate(pieces).astype(np.int32)
+    return {'index': index, 'forward': forward, 'backward': backward}
+
+
+def split_pack_tables(config=cfg.DEFAULT):
+    """The `emph_conv_split_pack_device` table of a step at 'bf16x3': int32
+    `index` [packs][23 040] into the flat parameter buffer, and {layer: pack
+    number} of the forward packs (`split_layer_names`) and of the
+    data-gradient packs W'[ci][co][j] = W[co][ci][2 - j] (the same layers but
+    the input layer).  Element ((tap * 5 + block) * 3 + m) * 512 + lane * 8 +
+    e of a pack is weight [32 m + lane % 32][16 block + 8 (lane / 32) + e]
+    [tap] of its layer, -1 (zeros) for rows 80 .. 95: the layout of
+    `emph_conv_split_pack`."""
+    check_supported(config)
+    offsets, _ = parameter_offsets(config)
+    tap, block, m, lane, e = np.meshgrid(
+        np.arange(3), np.arange(5), np.arange(3), np.arange(64), np.arange(8),
+        indexing='ij')
+    row = 32 * m + lane % 32
+    channel = 16 * block + 8 * (lane // 32) + e
+    inside = row < SPLIT_CHANNELS
+    row = np.minimum(row, SPLIT_CHANNELS - 1)
+    pieces, forward, backward = [], {}, {}
+    for direction, table in (('forward', forward), ('backward', backward)):
+        for name in split_layer_names(config):
+            if direction == 'backward' and name == 'input_layer':
+                continue
+            first, shape = offsets[f'{name}.weight']
+            assert tuple(shape) == (SPLIT_CHANNELS, SPLIT_CHANNELS, 3)
+            if direction == 'forward':
+                source = (row * SPLIT_CHANNELS + channel) * 3 + tap
+            else:
+                source = (channel * SPLIT_CHANNELS + row) * 3 + 2 - tap
+            table[name] = len(pieces)
+            pieces.append(np.where(inside, first + source, -1).ravel())
+    index = np.stack(pieces).astype(np.int32) if pieces else \
+        np.zeros((0, tap.size), dtype=np.int32)
     return {'index': index, 'forward': forward, 'backward': backward}
 
 
@@ -245,12 +319,16 @@ class Trainer:
     docstring for the two deviations."""
 
     def __init__(self, config=None, checkpoint=None, gpu=None, lr=1e-3,
-                 betas=(0.9, 0.999), eps=1e-8, seed=0):
-        """checkpoint: None (the reference's initialisation under `seed`), a
+                 betas=(0.9, 0.999), eps=1e-8, seed=0, precision='f32'):
+        """precision: 'f32' (default) or 'bf16x3' (see the module docstring);
+        a choice of the configuration, never of the batch, and not part of
+        the checkpoint: a run saved at one resumes at the other.
+        checkpoint: None (the reference's initialisation under `seed`), a
         state dict, or a file `weights.load` reads; a file written by `save`
         also restores the Adam moments and the step count."""
         self.config = config = config or api.active_config()
         check_supported(config)
+        self.precision = check_precision(precision)
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
         self.steps = 0
         optimizer = None
@@ -285,6 +363,21 @@ class Trainer:
             self._forward_packs = tables['forward']
             self._backward_packs = tables['backward']
             self._workspace = {}
+            self._split_forward, self._split_backward = {}, {}
+            if self.precision == 'bf16x3':
+                tables = split_pack_tables(config)
+                self._split_forward = tables['forward']
+                self._split_backward = tables['backward']
+                self._split_bytes = int(
+                    self.lib.emph_conv_split_pack_size())
+                assert tables['index'].shape[1] * 4 == self._split_bytes
+                self.split_index = torch.from_numpy(
+                    tables['index']).to(self.device)
+                self.split_packs = torch.zeros(
+                    (tables['index'].shape[0], self._split_bytes),
+                    dtype=torch.uint8, device=self.device)
+                self._zero_bias = torch.zeros(
+                    SPLIT_CHANNELS, dtype=torch.float32, device=self.device)
             self._repack()
 
     ###########################################################################
@@ -382,7 +475,8 @@ class Trainer:
         requests = [(runtime.AXIS_FRAMES, FRAME_TILE),
                     (runtime.AXIS_WORDS, WORD_TILE),
                     (runtime.AXIS_WORDS, GRAD_TILE)]
-        host, offsets = plan.pack_metadata(list(dict.fromkeys(requests)))
+        host, offsets = plan.pack_metadata(
+            list(dict.fromkeys(requests)), spans=self.precision == 'bf16x3')
         with torch.cuda.device(self.device):
             device_meta = torch.from_numpy(host).to(self.device)
         meta = {name: device_meta[start:start + size]
@@ -392,6 +486,11 @@ class Trainer:
 
     def _batch(self, arguments):
         if len(arguments) == 1 and isinstance(arguments[0], Batch):
+            if self._split_forward and 'conv_spans' not in arguments[0].meta:
+                raise ValueError(
+                    "the batch was prepared by a trainer at precision='f32' "
+                    "and carries no span table: prepare it with this "
+                    f"trainer (precision={self.precision!r})")
             return arguments[0]
         return self.prepare(*arguments)
 
@@ -431,6 +530,11 @@ class Trainer:
             self.parameters.data_ptr(), self.take_index.data_ptr(),
             self.packs.data_ptr(), self.packs.numel(), runtime.stream()),
             'emph_take')
+        if self._split_forward:
+            runtime.check(self.lib.emph_conv_split_pack_device(
+                self.parameters.data_ptr(), self.split_index.data_ptr(),
+                self.split_packs.data_ptr(), self.split_packs.shape[0],
+                runtime.stream()), 'emph_conv_split_pack_device')
 
     def _parameter(self, name):
         return self.parameters.data_ptr() + 4 * self.offsets[name][0]
@@ -446,6 +550,28 @@ class Trainer:
             tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS, tile, 0,
             runtime.stream()), 'emph_conv1d')
 
+    def _conv_split(self, pack, bias, x, y, ld, relu, spans):
+        """One Conv1d(80, 80, 3) on the frame axis as bf16x3: a launch of
+        `emph_conv1d_split` with a single layer, whose output is kept."""
+        runtime.check(self.lib.emph_conv1d_split(
+            x.data_ptr(), ld, y.data_ptr(), ld,
+            self.split_packs.data_ptr() + pack * self._split_bytes, bias, 1,
+            1 if relu else 0, spans.data_ptr(), spans.numel() // 8, None,
+            runtime.stream()), 'emph_conv1d_split')
+
+    def _frame_conv(self, name, x, y, ld, c_in, activation, batch):
+        """Forward of a frame-rate layer at the trainer's precision."""
+        if name in self._split_forward:
+            self._conv_split(
+                self._split_forward[name], self._parameter(f'{name}.bias'),
+                x, y, ld, activation == 'relu', batch.meta['conv_spans'])
+        else:
+            self._conv(
+                self._forward_packs[name], self._parameter(f'{name}.bias'),
+                x, y, ld, c_in, activation,
+                batch.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)],
+                FRAME_TILE)
+
     def _forward(self, batch):
         """The forward launches of a step; returns the step's buffers, whose
         'logits' then hold the packed logits [ld_words]."""
@@ -455,7 +581,6 @@ class Trainer:
         frames, words = runtime.AXIS_FRAMES, runtime.AXIS_WORDS
         buffers = self._buffers(plan)
         stream = runtime.stream()
-        frame_tiles = meta[('tiles', frames, FRAME_TILE)]
         word_tiles = meta[('tiles', words, WORD_TILE)]
         table, bounds = meta['table'], meta['bounds']
         word_segment = meta['word_segment']
@@ -465,13 +590,11 @@ class Trainer:
 
         # ---- forward, every layer's output kept (model/core.py:91-107,138)
         h, d = buffers['frames'], buffers['words']
-        self._conv(self._forward_packs['input_layer'],
-                   self._parameter('input_layer.bias'), batch.features, h[0],
-                   ld_f, config.num_features, None, frame_tiles, FRAME_TILE)
+        self._frame_conv('input_layer', batch.features, h[0], ld_f,
+                         config.num_features, None, batch)
         for i, name in enumerate(encoder):
-            self._conv(self._forward_packs[name],
-                       self._parameter(f'{name}.bias'), h[i], h[i + 1], ld_f,
-                       channels, 'relu', frame_tiles, FRAME_TILE)
+            self._frame_conv(name, h[i], h[i + 1], ld_f, channels, 'relu',
+                             batch)
         runtime.check(lib.emph_segment_reduce(
             h[layers].data_ptr(), ld_f, bounds.data_ptr(), d[0].data_ptr(),
             ld_w, channels, table.data_ptr(), word_segment.data_ptr(), ld_w,
@@ -532,9 +655,15 @@ class Trainer:
                     'emph_activation_backward')
                 self._weight_grad(dy, outputs[i], ld, channels, name,
                                   grad_tiles, buffers)
-                self._conv(self._backward_packs[name], None, dy,
-                           gradient[1 - current], ld, channels, None, tiles,
-                           tile)
+                if name in self._split_backward:
+                    self._conv_split(
+                        self._split_backward[name],
+                        self._zero_bias.data_ptr(), dy, gradient[1 - current],
+                        ld, False, meta['conv_spans'])
+                else:
+                    self._conv(self._backward_packs[name], None, dy,
+                               gradient[1 - current], ld, channels, None,
+                               tiles, tile)
                 current = 1 - current
             return gradient[current]
 
@@ -551,12 +680,14 @@ class Trainer:
                           'input_layer', frame_tiles, buffers)
 
     def _weight_grad(self, dy, x, ld, c_in, name, tiles, buffers):
-        runtime.check(self.lib.emph_conv_weight_grad(
+        split = name in self._split_forward
+        entry = 'emph_conv_weight_grad_split' if split else \
+            'emph_conv_weight_grad'
+        runtime.check(getattr(self.lib, entry)(
             dy.data_ptr(), ld, x.data_ptr(), ld, c_in, self.config.channels, 3,
             tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS, GRAD_TILE,
             buffers['slabs'].data_ptr(), self._gradient(f'{name}.weight'),
-            self._gradient(f'{name}.bias'), runtime.stream()),
-            'emph_conv_weight_grad')
+            self._gradient(f'{name}.bias'), runtime.stream()), entry)
 
     ###########################################################################
     # API
@@ -566,6 +697,7 @@ class Trainer:
         """The model's logits of a prepared `Batch`: the forward launches of a
         step alone (no loss, no gradient, no update).  Compact float32
         [total_words] on the device, the words of the items in order."""
+        batch = self._batch((batch,))
         with torch.cuda.device(self.device):
             packed = self._forward(batch)['logits']
             columns = torch.from_numpy(

@@ -3,7 +3,8 @@ resume, train, validate, save - around `Trainer.step`, fed by the resident
 loader of `emphases_amd.data`.
 
 Deviations from the reference, besides those of the step (`train/core.py`
-here: float32, every utterance alone):
+here: float32 or `precision='bf16x3'` in place of autocast, every utterance
+alone):
 
 * exactly `num_steps` updates.  The reference tests `step >= NUM_STEPS` after
   the update and before counting it (`train/core.py:172-177`), so a run whose
@@ -96,13 +97,17 @@ def evaluate(trainer, loader, log_steps=LOG_STEPS):
 def train(dataset, directory, gpu=None, *, partition_dir,
           cache_dir='data/cache', config=None, num_steps=NUM_STEPS,
           max_training_frames=MAX_TRAINING_FRAMES, log_interval=LOG_INTERVAL,
-          log_steps=LOG_STEPS, save_after=SAVE_AFTER, seed=RANDOM_SEED):
+          log_steps=LOG_STEPS, save_after=SAVE_AFTER, seed=RANDOM_SEED,
+          precision='f32'):
     """Train the convolution model on the 'train' partition of `dataset`,
     validating on its 'valid' partition (`emphases.train`); checkpoints and
-    `scalars.jsonl` go to `directory`.  Returns the final checkpoint's path."""
+    `scalars.jsonl` go to `directory`.  `precision`: 'f32' or 'bf16x3' of
+    `Trainer`, for the steps and for validation; the files do not record it.
+    Returns the final checkpoint's path."""
     from .. import data
     config = config or api.active_config()
     core.check_supported(config)        # before any file is read
+    core.check_precision(precision)
     directory = os.fspath(directory)
     os.makedirs(directory, exist_ok=True)
 
@@ -119,9 +124,11 @@ def train(dataset, directory, gpu=None, *, partition_dir,
         state = torch.load(path, map_location='cpu', weights_only=False)
         epoch, step = int(state['epoch']), int(state['step'])
         score, best = float(state['score']), float(state['best'])
-        trainer = core.Trainer(config, checkpoint=state, gpu=gpu)
+        trainer = core.Trainer(
+            config, checkpoint=state, gpu=gpu, precision=precision)
     else:
-        trainer = core.Trainer(config, gpu=gpu, seed=seed)
+        trainer = core.Trainer(
+            config, gpu=gpu, seed=seed, precision=precision)
     train_loader = loader('train', trainer, max_training_frames)
     # (the reference's validation sampler is `Sampler(dataset)`: the default
     # frame budget whatever the training one is, `data/sampler.py:15,35`)

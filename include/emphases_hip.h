@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 35
+#define EMPH_ABI_VERSION 36
 
 /* Segment-table fields */
 enum {
@@ -1155,6 +1155,35 @@ int emph_conv_weight_grad(const float* dy, int64_t ld_dy, const float* x, int64_
                           int32_t c_in, int32_t c_out, int32_t kernel_size,
                           const int32_t* tiles, int32_t n_tiles, int32_t tile_n,
                           float* workspace, float* dweight, float* dbias, void* stream);
+
+/* precision='bf16x3' of the training step: the reference trains these
+ * convolutions under torch.autocast with a GradScaler
+ * (emphases/train/core.py:78,111,136-142); here every fp32 operand is split
+ * into two bf16 pieces as in emph_conv1d_split (three products per term, fp32
+ * accumulation), parameters, gradients and Adam moments stay fp32.
+ *
+ * emph_conv_weight_grad_split replaces emph_conv_weight_grad for
+ * c_in = c_out = 80, kernel_size = 3 (anything else: EMPH_ERANGE, nothing is
+ * launched): the same tile table, the same emph_conv_weight_grad_parts slabs
+ * in `workspace`, added in the same fixed order, every element of dweight and
+ * dbias written, the same bits on every launch.  The products of dweight run
+ * on v_mfma_f32_16x16x32_bf16; dbias is summed in fp32.
+ *
+ * emph_conv_split_pack_device replaces emph_conv_split_pack (host) + a copy,
+ * and is to the split packs what emph_take is to the fp32 packs: ONE launch
+ * writes `count` packs of emph_conv_split_pack_size() bytes back to back
+ * (device, 16-byte aligned) from the flat parameter buffer `weights`;
+ * index int32 [count][emph_conv_split_pack_size() / 4], element
+ * ((tap * 5 + block) * 3 + m) * 512 + lane * 8 + e of a pack names the
+ * weight whose two pieces lie at that place of the pack (-1: zeros).  The
+ * bytes equal emph_conv_split_pack's for the same finite weights. */
+int emph_conv_weight_grad_split(const float* dy, int64_t ld_dy, const float* x, int64_t ldx,
+                                int32_t c_in, int32_t c_out, int32_t kernel_size,
+                                const int32_t* tiles, int32_t n_tiles, int32_t tile_n,
+                                float* workspace, float* dweight, float* dbias,
+                                void* stream);
+int emph_conv_split_pack_device(const float* weights, const int32_t* index, void* packs,
+                                int32_t count, void* stream);
 
 /* torch.optim.Adam's single-tensor update (train/core.py:40,139) over flat
  * buffers of `count` floats:

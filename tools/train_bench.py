@@ -1,6 +1,7 @@
 """One training step at the reference's training size, against PyTorch.
 
     python tools/train_bench.py [--laps 7] [--seconds 1.0] [--out profiles/train_step.json]
+    python tools/train_bench.py --precision bf16x3 --parent <checkout of the parent commit>
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --steps 20
 
 The batch is what the reference's sampler fills up to (`MAX_TRAINING_FRAMES =
@@ -18,6 +19,11 @@ Three contenders run in ALTERNATING laps of the same process on the same GPU:
   torch_autocast  the same under `torch.autocast` + `GradScaler`, as the
                   reference trains (`train/core.py:78,111,136-142`)
 
+With `--precision bf16x3` a fourth contender, `ours_bf16x3`, is the same
+trainer at that precision; with `--parent DIRECTORY` a child process runs the
+f32 step of the package in that checkout (built there) on the same batch,
+lap for lap between the others: `ours_parent`.
+
 Every utterance has the same lengths, so the padded batch of the torch model
 and the ragged batch of this package compute the same function.  A lap of one
 contender is timed with a pair of device events around `steps` steps, `steps`
@@ -29,7 +35,8 @@ import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.environ.get('EMPHASES_BENCH_ROOT') or os.path.dirname(
+    os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
@@ -108,6 +115,61 @@ def timed(function, steps):
     return begin.elapsed_time(end) / steps
 
 
+class Parent:
+    """The f32 step of another checkout of this package in a child process
+    (`--serve` of that checkout's copy of this batch and trainer, driven by
+    this file): a lap is a line to its stdin, the answer its ms per step."""
+
+    def __init__(self, directory):
+        import subprocess
+        directory = os.path.abspath(directory)
+        self.process = subprocess.Popen(
+            [sys.executable, os.path.abspath(__file__), '--serve'],
+            cwd=directory, env=dict(os.environ, EMPHASES_BENCH_ROOT=directory),
+            stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+
+    def ask(self, steps):
+        self.process.stdin.write(f'{steps}\n')
+        self.process.stdin.flush()
+        answer = self.process.stdout.readline()
+        if not answer.strip():
+            raise RuntimeError(
+                f'the parent checkout\'s process ended (exit status '
+                f'{self.process.wait()})')
+        return float(answer)
+
+    def __call__(self):
+        return self.ask(0)
+
+    def close(self):
+        self.process.stdin.close()
+        try:
+            self.process.wait(timeout=60)
+        except Exception:
+            self.process.kill()
+            self.process.wait()
+
+
+def run_lap(function, steps):
+    if isinstance(function, Parent):
+        return function.ask(steps)
+    return timed(function, steps)
+
+
+def serve():
+    """The child of `Parent`: 0 -> one step, its loss; n -> a timed lap."""
+    torch.cuda.set_device(0)
+    state = train.initial_state(emphases_amd.DEFAULT, seed=0)
+    ours = train.Trainer(checkpoint=state, gpu=0)
+    prepared = ours.prepare(*make_batch())
+    for line in sys.stdin:
+        steps = int(line)
+        if steps == 0:
+            print(float(ours.step(prepared)), flush=True)
+        else:
+            print(timed(lambda: ours.step(prepared), steps), flush=True)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument('--laps', type=int, default=7)
@@ -115,14 +177,37 @@ def main():
     parser.add_argument('--steps', type=int, default=None)
     parser.add_argument('--only', choices=('ours',), default=None)
     parser.add_argument('--out', default=None)
+    # (`--serve` also runs against the parent's package, which has no PRECISIONS)
+    parser.add_argument(
+        '--precision', default='f32',
+        choices=getattr(train, 'PRECISIONS', ('f32',)))
+    parser.add_argument('--parent', default=None)
+    parser.add_argument('--no-torch', action='store_true')
+    parser.add_argument('--serve', action='store_true', help=argparse.SUPPRESS)
     arguments = parser.parse_args()
+    if arguments.serve:
+        return serve()
     torch.cuda.set_device(0)
     batch = make_batch()
     state = train.initial_state(emphases_amd.DEFAULT, seed=0)
-    ours = train.Trainer(checkpoint=state, gpu=0)
+    if arguments.only:
+        ours = train.Trainer(
+            checkpoint=state, gpu=0, precision=arguments.precision)
+    else:
+        ours = train.Trainer(checkpoint=state, gpu=0)
     prepared = ours.prepare(*batch)
     contenders = {'ours': lambda: ours.step(prepared)}
-    if arguments.only is None:
+    if arguments.only is None and arguments.precision != 'f32':
+        split = train.Trainer(
+            checkpoint=state, gpu=0, precision=arguments.precision)
+        split_batch = split.prepare(*batch)
+        contenders[f'ours_{arguments.precision}'] = \
+            lambda: split.step(split_batch)
+    parent = None
+    if arguments.only is None and arguments.parent:
+        parent = Parent(arguments.parent)
+        contenders['ours_parent'] = parent
+    if arguments.only is None and not arguments.no_torch:
         features, _, bounds, _, targets = (item.cuda() for item in batch)
         frame = torch.arange(FRAMES, device='cuda')[None, :, None]
         membership = ((frame >= bounds[:, 0, None, :]) &
@@ -134,25 +219,30 @@ def main():
             contenders[name] = (
                 lambda m=model, o=optimizer, s=scaler: torch_step(
                     m, o, s, features, membership, targets))
-    first = {}
-    for name, function in contenders.items():
-        first[name] = float(function())
-        for _ in range(4):
-            function()
-    torch.cuda.synchronize()
-    steps = {}
-    for name, function in contenders.items():
-        probe = timed(function, 5)
-        steps[name] = arguments.steps or max(
-            5, int(arguments.seconds * 1e3 / probe))
-    if arguments.only:
-        timed(contenders['ours'], steps['ours'])
-        print(json.dumps({'ours_steps': steps['ours']}))
-        return
-    laps = {name: [] for name in contenders}
-    for _ in range(arguments.laps):
+    try:
+        first = {}
         for name, function in contenders.items():
-            laps[name].append(timed(function, steps[name]))
+            first[name] = float(function())
+            for _ in range(4):
+                function()
+        torch.cuda.synchronize()
+        steps = {}
+        for name, function in contenders.items():
+            probe = run_lap(function, 5)
+            steps[name] = arguments.steps or max(
+                5, int(arguments.seconds * 1e3 / probe))
+        if arguments.only:
+            timed(contenders['ours'], steps['ours'])
+            print(json.dumps({'ours_steps': steps['ours'],
+                              'precision': arguments.precision}))
+            return
+        laps = {name: [] for name in contenders}
+        for _ in range(arguments.laps):
+            for name, function in contenders.items():
+                laps[name].append(run_lap(function, steps[name]))
+    finally:
+        if parent is not None:
+            parent.close()
     record = {
         'batch': {'utterances': ITEMS, 'frames': FRAMES, 'words': WORDS},
         'device': torch.cuda.get_device_name(0),
@@ -163,9 +253,11 @@ def main():
                    'min': float(np.min(values)), 'max': float(np.max(values))}
             for name, values in laps.items()}}
     median = {name: record['ms_per_step'][name]['median'] for name in laps}
-    record['torch_fp32_over_ours'] = median['torch_fp32'] / median['ours']
-    record['torch_autocast_over_ours'] = \
-        median['torch_autocast'] / median['ours']
+    record['ms_per_step_laps'] = laps
+    if 'torch_fp32' in median:
+        record['torch_fp32_over_ours'] = median['torch_fp32'] / median['ours']
+        record['torch_autocast_over_ours'] = \
+            median['torch_autocast'] / median['ours']
     # executed MFMA flops of emph_conv_weight_grad per step: 64-position
     # tiles, 5 m-tiles x (3 x 5 + 1) n-tiles of 16 x 16 per k-step of 4
     tiles = ITEMS * -(-FRAMES // 64), ITEMS * -(-WORDS // 64)
