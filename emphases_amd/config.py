@@ -9,6 +9,8 @@ object handed to the operator layer.
 """
 import dataclasses
 import math
+import numbers
+from typing import Optional
 
 # Audio constants (defaults.py:47-74)
 SAMPLE_RATE = 16000
@@ -59,6 +61,10 @@ class Config:
     decoder_kernel_size: int = 3
     downsample_location: str = 'intermediate'
     downsample_method: str = 'sum'
+    # Dropout after every activation of the conv stacks (defaults.py:193,
+    # convolution.py:29-30): None builds no Dropout module; a probability
+    # (0. included) does.  Training only: the identity everywhere else
+    dropout: Optional[float] = None
     # Postprocess switch (defaults.py:227)
     loss: str = 'bce'
     # Transformer constants (transformer.py:18-23)
@@ -91,6 +97,13 @@ class Config:
                 'is not defined')
         if self.loss not in LOSSES:
             raise ValueError(f'Loss {self.loss} is not defined')
+        if self.dropout is not None and not (
+                isinstance(self.dropout, numbers.Real) and
+                not isinstance(self.dropout, bool) and
+                0 <= self.dropout < 1):
+            raise ValueError(
+                f'dropout must be None or a probability in [0, 1), not '
+                f'{self.dropout!r}')
         for k in (self.encoder_kernel_size, self.decoder_kernel_size):
             if k % 2 != 1 or not 1 <= k <= 7:
                 raise ValueError('kernel sizes must be odd and in 1..7')

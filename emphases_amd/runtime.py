@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -203,6 +203,10 @@ SIGNATURES = {
         _ptr, _ptr, _i64, _ptr, _ptr, _i32, _i32, _i64, _ptr, _ptr, _ptr,
         _i64, _ptr]),
     'emph_activation_backward': (_c.c_int, [_ptr, _ptr, _i64, _i32, _ptr]),
+    'emph_dropout': (_c.c_int, [
+        _ptr, _i64, _i64, _f32, _c.c_uint64, _c.c_uint32, _c.c_uint32, _ptr]),
+    'emph_activation_dropout_backward': (_c.c_int, [
+        _ptr, _ptr, _i64, _i32, _f32, _ptr]),
     'emph_segment_broadcast': (_c.c_int, [
         _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _i32, _i32, _ptr]),
     'emph_conv_weight_grad_parts': (_i32, [_i32]),

@@ -43,6 +43,10 @@ def parse_args(arguments=None):
         '--downsample_method', choices=('sum', 'average'),
         help="The word reduction: 'sum' (default) or 'average'")
     parser.add_argument(
+        '--dropout', type=float,
+        help='Dropout probability after every activation of the conv stacks '
+             '(0 <= p < 1; default: no Dropout modules)')
+    parser.add_argument(
         '--precision', choices=emphases_amd.train.PRECISIONS, default='f32',
         help="'f32' (default), or 'bf16x3': the frame-rate convolutions of "
              'the step on the bf16 matrix pipe, two pieces per operand')
@@ -52,7 +56,8 @@ def parse_args(arguments=None):
 def main(arguments=None):
     arguments = vars(parse_args(arguments))
     overrides = {
-        name: arguments.pop(name) for name in ('loss', 'downsample_method')}
+        name: arguments.pop(name)
+        for name in ('loss', 'downsample_method', 'dropout')}
     overrides = {
         name: value for name, value in overrides.items() if value is not None}
     if overrides:

@@ -13,6 +13,11 @@ library on one stream.  Deliberate, documented deviations:
   accumulation: `emph_conv1d_split`, `emph_conv_weight_grad_split`), while
   the word-rate layers, the output layer, the loss and Adam stay float32, as
   do the parameters, the gradients and the moments;
+* `Config.dropout` (`torch.nn.Dropout` after every activation of the two conv
+  stacks, `model/layers/convolution.py:29-30`) draws its masks from Philox
+  counters keyed by the trainer's seed, the layer and the step count
+  (`train/dropout.py`), not from torch's generator: a step can be repeated
+  and a resumed run continues the same masks;
 * every utterance is trained alone, with its own zero halo, exactly as
   inference runs it; the reference's padded batch leaks bias + ReLU of the
   padding into the last frames and words of every shorter utterance
@@ -39,6 +44,7 @@ from .. import config as cfg
 from .. import core as api
 from .. import runtime
 from .. import weights as weights_module
+from . import dropout as dropout_module
 
 FRAME_TILE = 64      # emph_conv1d, emph_conv_weight_grad, emph_segment_broadcast
 WORD_TILE = 32       # emph_conv1d on the word axis
@@ -110,6 +116,23 @@ def layer_names(config):
     return ['input_layer'] + [
         f'{prefix}.{2 * i}' for prefix in ('frame_encoder', 'word_decoder')
         for i in range(config.layers)]
+
+
+def checkpoint_names(config):
+    """Internal parameter name -> its name in a saved file: the reference's
+    `Convolution` is `Sequential(conv, activation[, Dropout])` per layer
+    (`convolution.py:25-33`, `DROPOUT is not None`, 0. included), so under
+    `Config.dropout` layer i of a stack is module 3 i, not 2 i.  `weights.load`
+    reads either numbering."""
+    stride = 2 if config.dropout is None else 3
+    names = collections.OrderedDict()
+    for name in weights_module.parameter_shapes(config):
+        prefix, _, rest = name.partition('.')
+        names[name] = name
+        if prefix in ('frame_encoder', 'word_decoder'):
+            index, kind = rest.split('.')
+            names[name] = f'{prefix}.{int(index) // 2 * stride}.{kind}'
+    return names
 
 
 def parameter_offsets(config):
@@ -323,6 +346,8 @@ class Trainer:
         """precision: 'f32' (default) or 'bf16x3' (see the module docstring);
         a choice of the configuration, never of the batch, and not part of
         the checkpoint: a run saved at one resumes at the other.
+        seed: of the initialisation (without a checkpoint) and of the dropout
+        masks (always; `Config.dropout`).
         checkpoint: None (the reference's initialisation under `seed`), a
         state dict, or a file `weights.load` reads; a file written by `save`
         also restores the Adam moments and the step count."""
@@ -331,6 +356,9 @@ class Trainer:
         self.precision = check_precision(precision)
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
         self.steps = 0
+        self.seed = int(seed)
+        # (None and 0. launch nothing: torch.nn.Dropout(0.) is the identity)
+        self.dropout = float(config.dropout or 0.)
         optimizer = None
         if checkpoint is None:
             state = initial_state(config, seed)
@@ -404,10 +432,13 @@ class Trainer:
         self.betas = tuple(float(b) for b in group['betas'])
 
     def state_dict(self):
-        """The parameters under the reference's names and shapes (CPU)."""
+        """The parameters under the reference's names (`checkpoint_names`)
+        and shapes (CPU)."""
         flat = self.parameters.cpu()
+        saved = checkpoint_names(self.config)
         return collections.OrderedDict(
-            (name, self._view(flat, name).clone()) for name in self.offsets)
+            (saved[name], self._view(flat, name).clone())
+            for name in self.offsets)
 
     def optimizer_state_dict(self):
         """`torch.optim.Adam.state_dict()` of the reference's optimizer
@@ -572,15 +603,26 @@ class Trainer:
                 batch.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)],
                 FRAME_TILE)
 
-    def _forward(self, batch):
+    def _dropout(self, name, y):
+        """`torch.nn.Dropout` on the kept output of layer `name`, in place:
+        the mask of this layer at this step (`train/dropout.py`)."""
+        runtime.check(self.lib.emph_dropout(
+            y.data_ptr(), y.numel(), 0, self.dropout,
+            self.seed & (1 << 64) - 1,
+            dropout_module.stream_of(self.config, name), self.steps,
+            runtime.stream()), 'emph_dropout')
+
+    def _forward(self, batch, training=False):
         """The forward launches of a step; returns the step's buffers, whose
-        'logits' then hold the packed logits [ld_words]."""
+        'logits' then hold the packed logits [ld_words].  `training`: with
+        the dropout masks of the step (never for validation)."""
         config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
         channels, layers = config.channels, config.layers
         ld_f, ld_w = plan.ld_frames, plan.ld_words
         frames, words = runtime.AXIS_FRAMES, runtime.AXIS_WORDS
         buffers = self._buffers(plan)
         stream = runtime.stream()
+        drop = training and self.dropout > 0.
         word_tiles = meta[('tiles', words, WORD_TILE)]
         table, bounds = meta['table'], meta['bounds']
         word_segment = meta['word_segment']
@@ -595,6 +637,8 @@ class Trainer:
         for i, name in enumerate(encoder):
             self._frame_conv(name, h[i], h[i + 1], ld_f, channels, 'relu',
                              batch)
+            if drop:
+                self._dropout(name, h[i + 1])
         runtime.check(lib.emph_segment_reduce(
             h[layers].data_ptr(), ld_f, bounds.data_ptr(), d[0].data_ptr(),
             ld_w, channels, table.data_ptr(), word_segment.data_ptr(), ld_w,
@@ -603,6 +647,8 @@ class Trainer:
             self._conv(self._forward_packs[name],
                        self._parameter(f'{name}.bias'), d[i], d[i + 1], ld_w,
                        channels, 'relu', word_tiles, WORD_TILE)
+            if drop:
+                self._dropout(name, d[i + 1])
         logits = buffers['logits']
         runtime.check(lib.emph_output_layer(
             d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
@@ -615,7 +661,7 @@ class Trainer:
         config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
         channels, layers = config.channels, config.layers
         ld_f, ld_w = plan.ld_frames, plan.ld_words
-        buffers = self._forward(batch)
+        buffers = self._forward(batch, training=True)
         stream = runtime.stream()
         frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
         word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
@@ -649,10 +695,16 @@ class Trainer:
             for i in range(len(names) - 1, -1, -1):
                 name = names[i]
                 dy = gradient[current]
-                runtime.check(lib.emph_activation_backward(
-                    outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
-                    runtime.ACTIVATIONS['relu'], stream),
-                    'emph_activation_backward')
+                if self.dropout > 0.:
+                    runtime.check(lib.emph_activation_dropout_backward(
+                        outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
+                        runtime.ACTIVATIONS['relu'], self.dropout, stream),
+                        'emph_activation_dropout_backward')
+                else:
+                    runtime.check(lib.emph_activation_backward(
+                        outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
+                        runtime.ACTIVATIONS['relu'], stream),
+                        'emph_activation_backward')
                 self._weight_grad(dy, outputs[i], ld, channels, name,
                                   grad_tiles, buffers)
                 if name in self._split_backward:

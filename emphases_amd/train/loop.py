@@ -124,8 +124,11 @@ def train(dataset, directory, gpu=None, *, partition_dir,
         state = torch.load(path, map_location='cpu', weights_only=False)
         epoch, step = int(state['epoch']), int(state['step'])
         score, best = float(state['score']), float(state['best'])
+        # (the seed keys the dropout masks; the step count, which the
+        # optimizer state restores, continues their stream)
         trainer = core.Trainer(
-            config, checkpoint=state, gpu=gpu, precision=precision)
+            config, checkpoint=state, gpu=gpu, seed=seed,
+            precision=precision)
     else:
         trainer = core.Trainer(
             config, gpu=gpu, seed=seed, precision=precision)

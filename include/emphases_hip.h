@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 36
+#define EMPH_ABI_VERSION 37
 
 /* Segment-table fields */
 enum {
@@ -1131,6 +1131,34 @@ int emph_output_layer_backward(const float* dlogit, const float* x, int64_t ldx,
  * (EMPH_ACT_RELU only).  count a multiple of 4, pointers 16-byte aligned. */
 int emph_activation_backward(const float* y, float* gradient, int64_t count,
                              int32_t activation, void* stream);
+
+/* Dropout of the training step (torch.nn.Dropout after every activation of
+ * the conv stacks, model/layers/convolution.py:29-30, when DROPOUT is set:
+ * config/hparam-search/dropout-{05,10}.py).  The mask is a specification
+ * (emphases_amd/train/dropout.py), not torch's random stream: for the flat
+ * buffer x[0 .. count), quad q = (origin + i) / 4 (64-bit) draws
+ * Philox-4x32-10 with counter (q_lo, q_hi, stream_id, step) and key
+ * (seed_lo, seed_hi); its four words belong to elements 4 q .. 4 q + 3 in
+ * order, and an element is kept iff its word >= min(round(p 2^32), 2^32 - 1).
+ * `stream_id` names the layer, `step` the number of updates already done.
+ *
+ * emph_dropout, in place: x[i] = kept ? x[i] * scale : +0.f with
+ * scale = float32(1 / (1 - p)) (formed in double, rounded once); a select, so
+ * that a dropped NaN or Inf of a padding column becomes 0.  The same
+ * arguments give the same bits on every launch.
+ *
+ * emph_activation_dropout_backward, in place: gradient[i] = y[i] > 0 ?
+ * gradient[i] * scale : 0 from the saved output y AFTER dropout, which is
+ * positive exactly where the pre-activation was positive and the element was
+ * kept: no mask is regenerated or stored (EMPH_ACT_RELU only).  With p = 0 it
+ * gives the bits of emph_activation_backward.
+ *
+ * Both: count and origin multiples of 4, pointers 16-byte aligned,
+ * 0 <= p < 1; anything else returns EMPH_EINVAL and launches nothing. */
+int emph_dropout(float* x, int64_t count, int64_t origin, float p, uint64_t seed,
+                 uint32_t stream_id, uint32_t step, void* stream);
+int emph_activation_dropout_backward(const float* y, float* gradient, int64_t count,
+                                     int32_t activation, float p, void* stream);
 
 /* Backward of emph_segment_reduce (emphases.downsample, core.py:426-469) for
  * EMPH_REDUCE_SUM / EMPH_REDUCE_AVERAGE: dx[c][t] = dword[c][w(t)] (divided by

@@ -2,6 +2,7 @@
 
     python tools/train_bench.py [--laps 7] [--seconds 1.0] [--out profiles/train_step.json]
     python tools/train_bench.py --precision bf16x3 --parent <checkout of the parent commit>
+    python tools/train_bench.py --dropout 0.1 --parent <checkout of the parent commit>
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --steps 20
 
 The batch is what the reference's sampler fills up to (`MAX_TRAINING_FRAMES =
@@ -23,6 +24,11 @@ With `--precision bf16x3` a fourth contender, `ours_bf16x3`, is the same
 trainer at that precision; with `--parent DIRECTORY` a child process runs the
 f32 step of the package in that checkout (built there) on the same batch,
 lap for lap between the others: `ours_parent`.
+
+With `--dropout P` one more contender, `ours_dropout`, is the same trainer
+under `Config(dropout=P)` (Philox masks, `emph_dropout`), and both torch
+models gain `torch.nn.Dropout(P)` after each activation, as the reference
+builds them under DROPOUT; `ours` stays the step without dropout.
 
 Every utterance has the same lengths, so the padded batch of the torch model
 and the ragged batch of this package compute the same function.  A lap of one
@@ -69,13 +75,19 @@ def make_batch(seed=0):
 class TorchModel(torch.nn.Module):
     """`emphases.Model` of the default configuration (`model/core.py`)."""
 
-    def __init__(self, state):
+    def __init__(self, state, dropout=None):
         super().__init__()
         conv = lambda c_in, c_out: torch.nn.Conv1d(  # noqa: E731
             c_in, c_out, kernel_size=3, padding='same')
+        # (`model/layers/convolution.py:25-33`: layer i is module 3 i under
+        # DROPOUT, 2 i without)
+        extra = [] if dropout is None else [torch.nn.Dropout(dropout)]
         stack = lambda: torch.nn.Sequential(*[  # noqa: E731
             module for _ in range(6)
-            for module in (conv(80, 80), torch.nn.ReLU())])
+            for module in [conv(80, 80), torch.nn.ReLU()] + extra])
+        if dropout is not None:
+            saved = train.checkpoint_names(emphases_amd.Config(dropout=dropout))
+            state = {saved[name]: value for name, value in state.items()}
         self.input_layer = conv(80, 80)
         self.frame_encoder = stack()
         self.word_decoder = stack()
@@ -182,6 +194,7 @@ def main():
         '--precision', default='f32',
         choices=getattr(train, 'PRECISIONS', ('f32',)))
     parser.add_argument('--parent', default=None)
+    parser.add_argument('--dropout', type=float, default=None)
     parser.add_argument('--no-torch', action='store_true')
     parser.add_argument('--serve', action='store_true', help=argparse.SUPPRESS)
     arguments = parser.parse_args()
@@ -190,9 +203,11 @@ def main():
     torch.cuda.set_device(0)
     batch = make_batch()
     state = train.initial_state(emphases_amd.DEFAULT, seed=0)
+    dropped = None if arguments.dropout is None else \
+        emphases_amd.Config(dropout=arguments.dropout)
     if arguments.only:
         ours = train.Trainer(
-            checkpoint=state, gpu=0, precision=arguments.precision)
+            dropped, checkpoint=state, gpu=0, precision=arguments.precision)
     else:
         ours = train.Trainer(checkpoint=state, gpu=0)
     prepared = ours.prepare(*batch)
@@ -203,6 +218,11 @@ def main():
         split_batch = split.prepare(*batch)
         contenders[f'ours_{arguments.precision}'] = \
             lambda: split.step(split_batch)
+    if arguments.only is None and dropped is not None:
+        masked = train.Trainer(
+            dropped, checkpoint=state, gpu=0, precision=arguments.precision)
+        masked_batch = masked.prepare(*batch)
+        contenders['ours_dropout'] = lambda: masked.step(masked_batch)
     parent = None
     if arguments.only is None and arguments.parent:
         parent = Parent(arguments.parent)
@@ -213,7 +233,7 @@ def main():
         membership = ((frame >= bounds[:, 0, None, :]) &
                       (frame < bounds[:, 1, None, :])).float()
         for name, mixed in (('torch_fp32', False), ('torch_autocast', True)):
-            model = TorchModel(state).cuda()
+            model = TorchModel(state, arguments.dropout).cuda()
             optimizer = torch.optim.Adam(model.parameters())
             scaler = torch.amp.GradScaler('cuda') if mixed else None
             contenders[name] = (
@@ -234,7 +254,8 @@ def main():
         if arguments.only:
             timed(contenders['ours'], steps['ours'])
             print(json.dumps({'ours_steps': steps['ours'],
-                              'precision': arguments.precision}))
+                              'precision': arguments.precision,
+                              'dropout': arguments.dropout}))
             return
         laps = {name: [] for name in contenders}
         for _ in range(arguments.laps):
@@ -247,6 +268,7 @@ def main():
         'batch': {'utterances': ITEMS, 'frames': FRAMES, 'words': WORDS},
         'device': torch.cuda.get_device_name(0),
         'laps': arguments.laps, 'steps_per_lap': steps,
+        'dropout': arguments.dropout, 'precision': arguments.precision,
         'first_loss': first,
         'ms_per_step': {
             name: {'median': float(np.median(values)),
@@ -254,6 +276,23 @@ def main():
             for name, values in laps.items()}}
     median = {name: record['ms_per_step'][name]['median'] for name in laps}
     record['ms_per_step_laps'] = laps
+    if 'ours_dropout' in median:
+        record['ours_dropout_over_ours'] = \
+            median['ours_dropout'] / median['ours']
+        if 'torch_fp32' in median:
+            record['torch_fp32_over_ours_dropout'] = \
+                median['torch_fp32'] / median['ours_dropout']
+            record['torch_autocast_over_ours_dropout'] = \
+                median['torch_autocast'] / median['ours_dropout']
+        # emph_dropout and emph_activation_dropout_backward per step: bytes
+        # read + written, and the 32 x 32 -> 64 integer multiplies of
+        # Philox-4x32-10 (2 a round, 10 rounds, per quad of elements)
+        # over the packed buffers [80, ld] of the 6 + 6 layers
+        elements = 6 * 80 * (
+            masked_batch.plan.ld_frames + masked_batch.plan.ld_words)
+        record['dropout_forward_bytes'] = 8 * elements
+        record['dropout_backward_bytes'] = 12 * elements
+        record['dropout_integer_multiplies'] = 20 * (elements // 4)
     if 'torch_fp32' in median:
         record['torch_fp32_over_ours'] = median['torch_fp32'] / median['ours']
         record['torch_autocast_over_ours'] = \
