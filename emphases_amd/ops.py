@@ -22,8 +22,34 @@ ops run the library's kernels on the library's packed layout (segments start
 16-aligned) and gather the result back into the caller's back-to-back layout;
 callers that own the layout use `engine.Engine` directly and skip both copies.
 No CPU implementation is registered: on a host tensor the dispatcher raises.
+
+Autograd.  `conv1d_same_act` (gradients of `x`, `weight`, `bias`) and
+`segment_reduce` (gradient of `x`) are differentiable once
+(`torch.library.register_autograd`; a backward under `create_graph=True`,
+the way to a second backward, raises) and carry a
+`register_fake` shape rule; `logmel`, `encoder_layer` and `prominence_forward`
+stay non-differentiable.  The backward runs on the library's kernels
+(`emph_activation_gradient`, `emph_conv_weight_grad_any`, `emph_conv1d` on the
+flipped pack, `emph_segment_reduce_backward`), without atomics: the same
+inputs give the same bits.
+
+Two paths of `conv1d_same_act`.  A weight that has never changed since the op
+first saw it (inference) takes the kernels it always took, its packs made
+once on the host.  A weight whose version has changed since (an optimizer
+updates it in place) is packed ON THE DEVICE (`emph_take` through an index
+table made once per weight shape, no device-to-host copy) and runs as
+direct-form `emph_conv1d` on 64-position tiles, as `train.Trainer` does.  The
+two paths differ at float32 rounding (Winograd against direct form).
+
+One plan per batch: the packed layout of a set of `cu_*` (and `bounds`)
+values, its device metadata and its device column indices are kept in a small
+LRU keyed by the bytes of those arrays and the device, so the layers of a
+model and their backwards share one upload.
 """
+import collections
 import functools
+import threading
+import weakref
 
 import numpy as np
 import torch
@@ -37,6 +63,10 @@ from . import weights as weights_module
 
 __all__ = ['logmel', 'conv1d_same_act', 'segment_reduce', 'encoder_layer',
            'prominence_forward']
+
+GRAD_TILE = 64       # emph_conv_weight_grad_any, emph_segment_reduce_backward
+DIRECT_TILE = 64     # emph_conv1d of the device-packed path and of the data gradient
+PLAN_CACHE_SIZE = 16
 
 
 def _counts(cu):
@@ -84,6 +114,76 @@ def _scatter(x, plan, offsets, counts, ld):
 def _gather(packed, offsets, counts):
     """The library's packed axis -> back-to-back columns (a fresh tensor)."""
     return packed.index_select(1, _columns(offsets, counts, packed.device))
+
+
+class _Layout:
+    """What the ops of one batch share: the `batch.Plan`, its integer metadata
+    on the device (name -> (view, size)), the frame tile tables (each uploaded
+    when an op first asks for its width, so a plan costs no more to build
+    than it did per call) and the device column indices of `_scatter` /
+    `_gather`."""
+
+    def __init__(self, plan, device):
+        self.plan = plan
+        host, offsets = plan.pack_metadata([])
+        self.buffer = torch.from_numpy(host).to(device)
+        self.meta = {name: (self.buffer[start:start + size], size)
+                     for name, (start, size) in offsets.items()}
+        self.meta['positions'] = (plan.total_frames, plan.total_words)
+        self.frame_columns = _columns(plan.frame_off, plan.frames, device)
+        self._word_columns = None
+        self.checked = {}
+
+    @property
+    def word_columns(self):
+        if self._word_columns is None:
+            self._word_columns = _columns(
+                self.plan.word_off, self.plan.words, self.buffer.device)
+        return self._word_columns
+
+    def view(self, name):
+        return self.meta[name][0]
+
+    def tiles(self, tile):
+        """(device tile table of the frame axis `tile` wide, its rows)."""
+        key = ('tiles', runtime.AXIS_FRAMES, tile)
+        if key not in self.meta:
+            host = np.ascontiguousarray(
+                self.plan.tiles(runtime.AXIS_FRAMES, tile)).ravel()
+            self.meta[key] = (
+                torch.from_numpy(host).to(self.buffer.device), host.size)
+        tiles, size = self.meta[key]
+        return tiles, size // runtime.TILE_FIELDS
+
+    def scatter(self, x, columns, ld):
+        """Back-to-back columns -> the library's packed axis (zeros between)."""
+        packed = torch.zeros((x.shape[0], ld), dtype=torch.float32,
+                             device=x.device)
+        packed.index_copy_(
+            1, columns, x[:, :columns.numel()].to(torch.float32))
+        return packed
+
+
+_layouts = collections.OrderedDict()
+_layouts_lock = threading.Lock()
+
+
+def _layout(device, frames, words=None, bounds=None):
+    """The `_Layout` of segments of `frames[i]` positions (and `words[i]` words
+    with `bounds`), from a small LRU keyed by the VALUES of the arrays."""
+    key = (device.index, frames.tobytes(),
+           None if words is None else (words.tobytes(), bounds.tobytes()))
+    with _layouts_lock:
+        found = _layouts.get(key)
+        if found is not None:
+            _layouts.move_to_end(key)
+            return found
+    found = _Layout(_frame_plan(frames, words, bounds), device)
+    with _layouts_lock:
+        _layouts[key] = found
+        while len(_layouts) > PLAN_CACHE_SIZE:
+            _layouts.popitem(last=False)
+    return found
 
 
 def _device_index(tensor):
@@ -146,6 +246,136 @@ def _conv_layer_cached(pointer, version, shape, bias_key, index, weight, bias):
         torch.device('cuda', index), winograd=True)
 
 
+def pack_index_tables(shape):
+    """The `emph_take` tables of a [c_out, c_in, k] weight (host, int32; -1:
+    zero): of the direct-form pack of the weight itself and of the pack of
+    W'[ci][co][j] = W[co][ci][k - 1 - j], whose `emph_conv1d` is the data
+    gradient."""
+    from .train import core as train_core
+    indices = np.arange(int(np.prod(shape)), dtype=np.int64).reshape(shape)
+    flipped = np.ascontiguousarray(indices.transpose(1, 0, 2)[:, :, ::-1])
+    return (train_core._pack_indices(indices).astype(np.int32),
+            train_core._pack_indices(flipped).astype(np.int32))
+
+
+@functools.lru_cache(maxsize=32)
+def _device_tables(shape, index):
+    return tuple(torch.from_numpy(table).to(torch.device('cuda', index))
+                 for table in pack_index_tables(shape))
+
+
+class _ByStorage:
+    """A small LRU keyed by a tensor's (address, shape, strides, ...) that can
+    never answer for ANOTHER tensor: every entry holds a weak reference to the
+    storage it was made from and is a hit only while that very storage is
+    alive and is the asking tensor's.  (An address alone is not an identity:
+    the caching allocator hands the address of a dropped weight to the next
+    one of the same shape.)  Entries of dead storages are dropped as they are
+    met.  One lock for every instance.  (Relies on torch returning the SAME
+    Python object from `tensor.untyped_storage()` for as long as the storage
+    lives; on a torch that made a new object per call every lookup would miss
+    - still correct, but the weight would be packed again on every call.)"""
+
+    lock = threading.Lock()
+
+    def __init__(self, size):
+        self.size = size
+        self.entries = collections.OrderedDict()
+
+    @staticmethod
+    def key(tensor, *more):
+        return (tensor.data_ptr(), tuple(tensor.shape), tuple(tensor.stride()),
+                str(tensor.device)) + more
+
+    def get(self, tensor, key):
+        storage = tensor.untyped_storage()
+        with self.lock:
+            found = self.entries.get(key)
+            if found is None:
+                return None
+            if found[0]() is not storage:
+                del self.entries[key]       # another tensor lived here
+                return None
+            self.entries.move_to_end(key)
+            return found[1]
+
+    def put(self, tensor, key, value):
+        with self.lock:
+            self.entries[key] = (weakref.ref(tensor.untyped_storage()), value)
+            self.entries.move_to_end(key)
+            while len(self.entries) > self.size:
+                self.entries.popitem(last=False)
+        return value
+
+
+_device_packs = _ByStorage(64)
+_first_versions = _ByStorage(256)
+
+
+def _device_pack(weight, index, flipped):
+    """The direct-form MFMA pack of `weight` (or of its flipped transpose),
+    built on the device by one `emph_take`; kept per (storage, version)."""
+    key = _ByStorage.key(weight, weight._version, flipped)
+    found = _device_packs.get(weight, key)
+    if found is not None:
+        return found
+    table = _device_tables(tuple(weight.shape), index)[1 if flipped else 0]
+    source = weight.detach()
+    if source.dtype != torch.float32 or not source.is_contiguous():
+        source = source.to(torch.float32).contiguous()
+    pack = torch.empty(table.numel(), dtype=torch.float32, device=weight.device)
+    runtime.check(runtime.library().emph_take(
+        source.data_ptr(), table.data_ptr(), pack.data_ptr(), pack.numel(),
+        runtime.stream()), 'emph_take')
+    return _device_packs.put(weight, key, pack)
+
+
+def _weight_changes(weight):
+    """Whether the version of `weight` has changed since the op first saw its
+    storage: the weight is being trained (the op cannot see `requires_grad`
+    below the autograd key)."""
+    key = _ByStorage.key(weight)
+    first = _first_versions.get(weight, key)
+    if first is None:
+        first = _first_versions.put(weight, key, (weight._version,))
+    return first[0] != weight._version
+
+
+def _activation(activation):
+    activation = None if activation in ('none', '') else activation
+    if activation is not None and activation not in cfg.ACTIVATIONS:
+        raise ValueError(f'Activation {activation} is not defined')
+    return activation
+
+
+def _conv_layout(x, cu_T):
+    counts, _ = _counts(cu_T)
+    if int(counts.sum()) != x.shape[1]:
+        raise ValueError('cu_T does not cover the columns of x')
+    return _layout(x.device, counts)
+
+
+def _float_pointer(tensor, keep):
+    """Device address of a float32 contiguous view of `tensor` (kept alive in
+    the list `keep`); None for None."""
+    if tensor is None:
+        return None
+    tensor = tensor.detach()
+    if tensor.dtype != torch.float32 or not tensor.is_contiguous():
+        tensor = tensor.to(torch.float32).contiguous()
+    keep.append(tensor)
+    return tensor.data_ptr()
+
+
+def _direct_conv(packed, out, ld, pack, bias, c_in, c_out, kernel_size,
+                 activation, layout):
+    tiles, n_tiles = layout.tiles(DIRECT_TILE)
+    runtime.check(runtime.library().emph_conv1d(
+        packed.data_ptr(), ld, out.data_ptr(), ld, pack.data_ptr(), bias, c_in,
+        c_out, kernel_size, runtime.ACTIVATIONS[activation], tiles.data_ptr(),
+        n_tiles, DIRECT_TILE, 0, runtime.stream()), 'emph_conv1d')
+
+
 @torch.library.custom_op('emphases_amd::conv1d_same_act', mutates_args=())
 def conv1d_same_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
                     cu_T: torch.Tensor, activation: str) -> torch.Tensor:
@@ -154,33 +384,161 @@ def conv1d_same_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
     zero halo: x `[C_in, sum T_i]`, weight `[C_out, C_in, k]`, bias `[C_out]`
     -> `[C_out, sum T_i]`.  activation: 'none' | 'relu' | 'gelu' | 'silu' |
     'leaky_relu'.  The packed weights are cached per (weight storage,
-    version)."""
+    version): on the host for a weight that never changed, on the device
+    (direct-form `emph_conv1d`) for one that has - see the module docstring.
+
+    Backward (once): the activation gradient is applied to dy in place - from
+    the saved output for relu / leaky_relu; for gelu / silu the
+    pre-activation is RECOMPUTED by one `emph_conv1d` with no activation;
+    dW / db come from `emph_conv_weight_grad_any` for every shape (Conv1d(.,
+    80, 3) included: one kernel for the general path, the specialised
+    `emph_conv_weight_grad` stays `Trainer`'s); dx is `emph_conv1d` on the
+    device pack of W'[ci][co][j] = W[co][ci][k - 1 - j] without bias.  Only
+    the gradients `needs_input_grad` asks for are computed."""
     index = _device_index(x)
-    counts, _ = _counts(cu_T)
-    if int(counts.sum()) != x.shape[1]:
-        raise ValueError('cu_T does not cover the columns of x')
-    activation = None if activation in ('none', '') else activation
-    if activation is not None and activation not in cfg.ACTIVATIONS:
-        raise ValueError(f'Activation {activation} is not defined')
+    activation = _activation(activation)
+    layout = _conv_layout(x, cu_T)
+    plan = layout.plan
     engine = core.get_engine(None, index, cfg.DEFAULT)
-    layer = _cached_conv(weight, bias, index)
-    plan = _frame_plan(counts)
     with torch.cuda.device(index), engine.lock:
-        tile = 64 if (layer.winograd4 is not None and engine.quad and
-                      activation in (None, 'relu')) else \
-            32 if layer.winograd is not None else 16
-        host, offsets = plan.pack_metadata([(runtime.AXIS_FRAMES, tile)])
-        device_meta = torch.from_numpy(host).to(x.device)
-        meta = {name: (device_meta[start:start + size], size)
-                for name, (start, size) in offsets.items()}
-        meta['positions'] = (plan.total_frames, plan.total_words)
-        packed = _scatter(x.to(torch.float32), plan, plan.frame_off, plan.frames,
-                          plan.ld_frames)
-        out = torch.zeros((layer.c_out, plan.ld_frames), dtype=torch.float32,
-                          device=x.device)
-        engine._conv(layer, packed, plan.ld_frames, out, plan.ld_frames, meta,
-                     runtime.AXIS_FRAMES, tile, activation)
-        return _gather(out, plan.frame_off, plan.frames)
+        packed = layout.scatter(x, layout.frame_columns, plan.ld_frames)
+        out = torch.zeros((weight.shape[0], plan.ld_frames),
+                          dtype=torch.float32, device=x.device)
+        if _weight_changes(weight):
+            c_out, c_in, kernel_size = weight.shape
+            keep = []
+            _direct_conv(packed, out, plan.ld_frames,
+                         _device_pack(weight, index, False),
+                         _float_pointer(bias, keep), c_in, c_out, kernel_size,
+                         activation, layout)
+        else:
+            layer = _cached_conv(weight, bias, index)
+            tile = 64 if (layer.winograd4 is not None and engine.quad and
+                          activation in (None, 'relu')) else \
+                32 if layer.winograd is not None else 16
+            layout.tiles(tile)
+            engine._conv(layer, packed, plan.ld_frames, out, plan.ld_frames,
+                         layout.meta, runtime.AXIS_FRAMES, tile, activation)
+        return out.index_select(1, layout.frame_columns)
+
+
+@conv1d_same_act.register_fake
+def _conv1d_same_act_fake(x, weight, bias, cu_T, activation):
+    return x.new_empty((weight.shape[0], x.shape[1]), dtype=torch.float32)
+
+
+def _once(name):
+    """The backward of `name` runs on HIP kernels that record no graph: asking
+    for one (`create_graph=True`, the way to a second backward) raises."""
+    if torch.is_grad_enabled():
+        raise RuntimeError(
+            f'emphases_amd::{name} is differentiable once: its backward '
+            'records no graph (create_graph=True / a second backward is not '
+            'supported)')
+
+
+def _conv_setup(ctx, inputs, output):
+    x, weight, bias, cu_T, activation = inputs
+    ctx.activation = activation
+    # (only relu / leaky_relu read the saved output)
+    ctx.save_for_backward(
+        x, weight, bias, cu_T,
+        output if activation in ('relu', 'leaky_relu') else None)
+
+
+def _conv_backward(ctx, grad):
+    _once('conv1d_same_act')
+    x, weight, bias, cu_T, output = ctx.saved_tensors
+    need_x, need_weight, need_bias = ctx.needs_input_grad[:3]
+    index = _device_index(grad)
+    activation = _activation(ctx.activation)
+    layout = _conv_layout(x, cu_T)
+    plan, ld = layout.plan, layout.plan.ld_frames
+    c_out, c_in, kernel_size = weight.shape
+    lib = runtime.library()
+    dx = dweight = dbias = None
+    with torch.cuda.device(index):
+        stream = runtime.stream()
+        dy = layout.scatter(grad, layout.frame_columns, ld)
+        packed = None
+        if need_weight or need_bias or activation in ('gelu', 'silu'):
+            packed = layout.scatter(x, layout.frame_columns, ld)
+        if activation in ('relu', 'leaky_relu'):
+            source = layout.scatter(output, layout.frame_columns, ld)
+        elif activation is not None:
+            keep = []
+            source = torch.zeros_like(dy)
+            _direct_conv(packed, source, ld, _device_pack(weight, index, False),
+                         _float_pointer(bias, keep), c_in, c_out, kernel_size,
+                         None, layout)
+        if activation is not None:
+            runtime.check(lib.emph_activation_gradient(
+                source.data_ptr(), dy.data_ptr(), dy.numel(),
+                runtime.ACTIVATIONS[activation], stream),
+                'emph_activation_gradient')
+        if need_weight or need_bias:
+            tiles, n_tiles = layout.tiles(GRAD_TILE)
+            dweight = torch.empty((c_out, c_in, kernel_size),
+                                  dtype=torch.float32, device=grad.device)
+            dbias = torch.empty(c_out, dtype=torch.float32, device=grad.device)
+            if n_tiles:
+                workspace = torch.empty(
+                    int(lib.emph_conv_weight_grad_any_workspace(
+                        c_in, c_out, kernel_size, n_tiles)),
+                    dtype=torch.float32, device=grad.device)
+                runtime.check(lib.emph_conv_weight_grad_any(
+                    dy.data_ptr(), ld, packed.data_ptr(), ld, c_in, c_out,
+                    kernel_size, tiles.data_ptr(), n_tiles, GRAD_TILE,
+                    workspace.data_ptr(), dweight.data_ptr(), dbias.data_ptr(),
+                    stream), 'emph_conv_weight_grad_any')
+            else:
+                dweight.zero_()
+                dbias.zero_()
+            dweight = dweight.to(weight.dtype) if need_weight else None
+            dbias = dbias.to(bias.dtype) if need_bias else None
+        if need_x:
+            dpacked = torch.zeros((c_in, ld), dtype=torch.float32,
+                                  device=grad.device)
+            _direct_conv(dy, dpacked, ld, _device_pack(weight, index, True),
+                         None, c_out, c_in, kernel_size, None, layout)
+            dx = dpacked.index_select(1, layout.frame_columns).to(x.dtype)
+    return dx, dweight, dbias, None, None
+
+
+conv1d_same_act.register_autograd(_conv_backward, setup_context=_conv_setup)
+
+
+def _reduce_layout(x, bounds, cu_frames, cu_words, mode):
+    if mode not in cfg.DOWNSAMPLE_METHODS:
+        raise ValueError(f'Interpolation method {mode} is not defined')
+    frames, _ = _counts(cu_frames)
+    words, _ = _counts(cu_words)
+    if len(frames) != len(words):
+        raise ValueError('cu_frames and cu_words describe different numbers of segments')
+    host_bounds = np.ascontiguousarray(
+        bounds.detach().cpu().to(torch.int64).numpy().reshape(2, -1))
+    layout = _layout(x.device, frames, words, host_bounds)
+    if ('forward', mode) not in layout.checked:
+        engine_module.check_bounds(layout.plan, mode)
+        layout.checked['forward', mode] = True
+    return layout
+
+
+def check_backward_bounds(plan):
+    """ValueError unless the words of every segment are sorted, non-empty and
+    do not overlap: what `emph_segment_reduce_backward` needs to give every
+    frame one word at the most (the forward accepts any words)."""
+    first = 0
+    for index, count in enumerate(plan.words):
+        starts, ends = plan.segment_bounds[:, first:first + int(count)]
+        first += int(count)
+        if np.any(ends <= starts):
+            raise ValueError(
+                f'segment {index}: a word with end <= start has no backward')
+        if np.any(starts[1:] < ends[:-1]):
+            raise ValueError(
+                f'segment {index}: words overlap or are not in order; the '
+                'backward of segment_reduce needs sorted, disjoint words')
 
 
 @torch.library.custom_op('emphases_amd::segment_reduce', mutates_args=())
@@ -189,33 +547,78 @@ def segment_reduce(x: torch.Tensor, bounds: torch.Tensor, cu_frames: torch.Tenso
     """`emphases.downsample` (`core.py:426-469`): x `[C, sum F_i]`, bounds int
     `[2, sum W_i]` (frames relative to the word's own segment), mode 'sum' |
     'average' | 'max' | 'center' -> `[C, sum W_i]`.  An empty word: 0 (sum),
-    NaN (average), as in the reference; 'max' of an empty word raises."""
+    NaN (average), as in the reference; 'max' of an empty word raises.
+
+    Backward (once, `emph_segment_reduce_backward`): the gradient of x; it
+    raises ValueError on the host if the words of a segment overlap, are out
+    of order or include a word with end <= start, all of which the forward
+    accepts: the backward finds a frame's word by bisection over the starts,
+    and an empty word would hide the word around it."""
     index = _device_index(x)
-    if mode not in cfg.DOWNSAMPLE_METHODS:
-        raise ValueError(f'Interpolation method {mode} is not defined')
-    frames, _ = _counts(cu_frames)
-    words, _ = _counts(cu_words)
-    if len(frames) != len(words):
-        raise ValueError('cu_frames and cu_words describe different numbers of segments')
-    host_bounds = bounds.detach().cpu().to(torch.int64).numpy().reshape(2, -1)
-    plan = _frame_plan(frames, words, host_bounds)
-    engine_module.check_bounds(plan, mode)
+    layout = _reduce_layout(x, bounds, cu_frames, cu_words, mode)
+    plan = layout.plan
     lib = runtime.library()
     with torch.cuda.device(index):
-        host, offsets = plan.pack_metadata([])
-        meta = torch.from_numpy(host).to(x.device)
-        view = lambda name: meta[  # noqa: E731
-            offsets[name][0]:offsets[name][0] + offsets[name][1]]
-        packed = _scatter(x.to(torch.float32), plan, plan.frame_off, plan.frames,
-                          plan.ld_frames)
+        packed = layout.scatter(x, layout.frame_columns, plan.ld_frames)
         out = torch.zeros((x.shape[0], plan.ld_words), dtype=torch.float32,
                           device=x.device)
         runtime.check(lib.emph_segment_reduce(
-            packed.data_ptr(), plan.ld_frames, view('bounds').data_ptr(),
-            out.data_ptr(), plan.ld_words, x.shape[0], view('table').data_ptr(),
-            view('word_segment').data_ptr(), plan.ld_words,
+            packed.data_ptr(), plan.ld_frames, layout.view('bounds').data_ptr(),
+            out.data_ptr(), plan.ld_words, x.shape[0],
+            layout.view('table').data_ptr(),
+            layout.view('word_segment').data_ptr(), plan.ld_words,
             runtime.REDUCTIONS[mode], runtime.stream()), 'emph_segment_reduce')
-        return _gather(out, plan.word_off, plan.words)
+        return out.index_select(1, layout.word_columns)
+
+
+@segment_reduce.register_fake
+def _segment_reduce_fake(x, bounds, cu_frames, cu_words, mode):
+    return x.new_empty((x.shape[0], bounds.shape[1]), dtype=torch.float32)
+
+
+def _reduce_setup(ctx, inputs, output):
+    x, bounds, cu_frames, cu_words, mode = inputs
+    ctx.mode = mode
+    ctx.save_for_backward(x, bounds, cu_frames, cu_words,
+                          output if mode == 'max' else None)
+
+
+def _reduce_backward(ctx, grad):
+    _once('segment_reduce')
+    x, bounds, cu_frames, cu_words, output = ctx.saved_tensors
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None, None
+    index = _device_index(grad)
+    mode = ctx.mode
+    layout = _reduce_layout(x, bounds, cu_frames, cu_words, mode)
+    if 'backward' not in layout.checked:
+        check_backward_bounds(layout.plan)
+        layout.checked['backward'] = True
+    plan = layout.plan
+    lib = runtime.library()
+    with torch.cuda.device(index):
+        dword = layout.scatter(grad, layout.word_columns, plan.ld_words)
+        packed = top = None
+        if mode == 'max':
+            packed = layout.scatter(x, layout.frame_columns, plan.ld_frames)
+            top = layout.scatter(output, layout.word_columns, plan.ld_words)
+        dpacked = torch.zeros((x.shape[0], plan.ld_frames), dtype=torch.float32,
+                              device=grad.device)
+        tiles, n_tiles = layout.tiles(GRAD_TILE)
+        runtime.check(lib.emph_segment_reduce_backward(
+            dword.data_ptr(), plan.ld_words, layout.view('bounds').data_ptr(),
+            None if packed is None else packed.data_ptr(), plan.ld_frames,
+            None if top is None else top.data_ptr(), dpacked.data_ptr(),
+            plan.ld_frames, x.shape[0], layout.view('table').data_ptr(),
+            tiles.data_ptr(), n_tiles, runtime.REDUCTIONS[mode],
+            runtime.stream()), 'emph_segment_reduce_backward')
+        dx = dpacked.index_select(1, layout.frame_columns).to(x.dtype)
+        if dx.shape[1] < x.shape[1]:      # (columns past the last segment)
+            dx = torch.nn.functional.pad(dx, (0, x.shape[1] - dx.shape[1]))
+    return dx, None, None, None, None
+
+
+segment_reduce.register_autograd(_reduce_backward, setup_context=_reduce_setup)
 
 
 _LAYER_NAMES = ('self_attn.in_proj_weight', 'self_attn.in_proj_bias',

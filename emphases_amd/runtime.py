@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -217,6 +217,14 @@ SIGNATURES = {
         _ptr, _i64, _ptr, _i64, _i32, _i32, _i32, _ptr, _i32, _i32, _ptr,
         _ptr, _ptr, _ptr]),
     'emph_conv_split_pack_device': (_c.c_int, [_ptr, _ptr, _ptr, _i32, _ptr]),
+    'emph_conv_weight_grad_any_workspace': (_i64, [_i32, _i32, _i32, _i32]),
+    'emph_conv_weight_grad_any': (_c.c_int, [
+        _ptr, _i64, _ptr, _i64, _i32, _i32, _i32, _ptr, _i32, _i32, _ptr,
+        _ptr, _ptr, _ptr]),
+    'emph_segment_reduce_backward': (_c.c_int, [
+        _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _ptr,
+        _i32, _i32, _ptr]),
+    'emph_activation_gradient': (_c.c_int, [_ptr, _ptr, _i64, _i32, _ptr]),
     'emph_adam_step': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _i64, _c.c_double, _c.c_double, _f32, _f32,
         _f32, _ptr]),

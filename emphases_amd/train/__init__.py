@@ -1,7 +1,9 @@
 """Training the convolution model on the GPU (`emphases.train`): the step -
 forward with every layer kept, masked loss, backward and Adam
 (`emphases/train/core.py:91-142`) - and the loop around it - resume, train,
-validate, save (`train/core.py:13-307`) - fed by `emphases_amd.data`."""
+validate, save (`train/core.py:13-307`) - fed by `emphases_amd.data`; and
+`TorchModel`, the same architecture as a `torch.nn.Module` on the
+differentiable operator seams for the configurations the fused step refuses."""
 from .core import (  # noqa: F401
     PRECISIONS, Batch, Trainer, adam_state_dict, check_batch,
     check_precision, check_supported, checkpoint_names, gather_tables,
@@ -9,4 +11,6 @@ from .core import (  # noqa: F401
     layer_names, parameter_offsets, split_layer_names, split_pack_tables,
     write_checkpoint)
 from . import dropout  # noqa: F401
+from .model import (  # noqa: F401
+    TorchModel, check_model_supported, initial_model_state, loss_fn)
 from .loop import evaluate, latest_path, train  # noqa: F401

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 37
+#define EMPH_ABI_VERSION 38
 
 /* Segment-table fields */
 enum {
@@ -1223,6 +1223,73 @@ int emph_conv_split_pack_device(const float* weights, const int32_t* index, void
 int emph_adam_step(float* parameter, const float* gradient, float* exp_avg,
                    float* exp_avg_sq, int64_t count, double beta1, double beta2,
                    float step_size, float correction2_sqrt, float eps, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* Backward of the operator seams (emphases_amd/ops.py under autograd)       */
+/* ------------------------------------------------------------------------ */
+
+/* The reference trains every configuration of config/downsample/ and
+ * config/hparam-search/ through autograd (emphases/train/core.py:136).  These
+ * entry points are the backward of emph_conv1d and emph_segment_reduce for
+ * the shapes, activations and reductions the fused step above does not
+ * cover.  No floating-point atomics, no hand-off between workgroups: the
+ * same inputs give the same bits on every launch.
+ *
+ * emph_conv_weight_grad_any is emph_conv_weight_grad with the shape as an
+ * argument (model/layers/convolution.py:25-28 under autograd):
+ *   dweight[co][ci][j] = sum_t dy[co][t] x[ci][t + j - (k - 1) / 2]
+ *   dbias[co] = sum_t dy[co][t]
+ * inside every segment of the 64-wide tile table `tiles` (tile_n = 64), x
+ * zero outside its segment (selected, never multiplied: what lies in the
+ * padding columns, NaN included, reaches no result); c_in and c_out in
+ * 1..128, kernel_size in {1, 3, 5, 7}, either axis.  Anything else returns
+ * EMPH_ERANGE and launches nothing.  Two launches: the first writes
+ * emph_conv_weight_grad_parts(n_tiles) slabs of c_out (k c_in) + c_out floats
+ * into `workspace` (emph_conv_weight_grad_any_workspace floats; 0 for a shape
+ * out of range), the second adds them in a fixed order that depends on their
+ * number alone.  Every element of dweight and dbias is written. */
+int64_t emph_conv_weight_grad_any_workspace(int32_t c_in, int32_t c_out, int32_t kernel_size,
+                                            int32_t n_tiles);
+int emph_conv_weight_grad_any(const float* dy, int64_t ld_dy, const float* x, int64_t ldx,
+                              int32_t c_in, int32_t c_out, int32_t kernel_size,
+                              const int32_t* tiles, int32_t n_tiles, int32_t tile_n,
+                              float* workspace, float* dweight, float* dbias, void* stream);
+
+/* Backward of emph_segment_reduce (emphases.downsample, core.py:426-469) for
+ * all four modes.  `dword` [channels][ldw] and `bounds` [2][ldw] as the
+ * forward's `out` and `bounds`, `tiles` the 64-wide tile table of the frame
+ * axis, `x` [channels][ldx] and `y` [channels][ldw] the forward's input and
+ * output (read for EMPH_REDUCE_MAX only; may be null otherwise).  dx is
+ * written for every column inside a segment: 0 where no word covers the
+ * frame.  `end` beyond the chunk is clamped as the forward clamps it.
+ *   SUM      dx[c][t] = dword[c][w(t)]
+ *   AVERAGE  dx[c][t] = dword[c][w(t)] * (1 / (end - start))
+ *            (both: the bits of emph_segment_broadcast for bounds inside the
+ *            chunk)
+ *   CENTER   dword[c][w] goes to frame (start + end) // 2
+ *   MAX      dword[c][w] goes to the first frame of [start, end) whose value
+ *            equals y[c][w], torch's tie rule for max(dim).  The forward's
+ *            fmaxf skips a NaN, so y is the maximum of the other frames and a
+ *            NaN frame receives 0; a word of NaN alone has y = -inf, which no
+ *            frame equals: its gradient is dropped.
+ * The words of a segment must be sorted and must not overlap (a frame has
+ * one word at the most): every dx element is written by one thread. */
+int emph_segment_reduce_backward(const float* dword, int64_t ldw, const int32_t* bounds,
+                                 const float* x, int64_t ldx, const float* y, float* dx,
+                                 int64_t ld_dx, int32_t channels, const int64_t* seg,
+                                 const int32_t* tiles, int32_t n_tiles, int32_t mode,
+                                 void* stream);
+
+/* Gradient of the activation of model/layers/convolution.py:28, in place:
+ * gradient[i] *= act'(.).  EMPH_ACT_RELU (the bits of
+ * emph_activation_backward) and EMPH_ACT_LEAKY_RELU (slope 0.01) read the
+ * saved OUTPUT in `source`, whose sign is the sign of the pre-activation;
+ * EMPH_ACT_GELU (exact erf form: cdf + x pdf) and EMPH_ACT_SILU
+ * (s (1 + x (1 - s)), s = sigmoid(x)) read the PRE-ACTIVATION.
+ * EMPH_ACT_NONE launches nothing.  count a multiple of 4, pointers 16-byte
+ * aligned, as emph_activation_backward. */
+int emph_activation_gradient(const float* source, float* gradient, int64_t count,
+                             int32_t activation, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Measurement                                                               */
