@@ -98,7 +98,11 @@ int emph_prominence_forward(const emph_conv_model* model, const void* audio,
                        m.encoder_biases == m.input_bias + c &&
                        (m.activation == EMPH_ACT_RELU || m.activation == EMPH_ACT_NONE);
     if (stack) {
-        const int total = 1 + m.encoder_layers;
+        // model->compose: the input layer and encoder layer 0 are one (5-tap) layer
+        // of the first launch, emph_conv1d_stack_composed
+        const bool composed = m.compose != nullptr && m.encoder_layers >= 1;
+        const int skip = composed ? 1 : 0;      // layers of the model the first one swallows
+        const int total = 1 + m.encoder_layers - skip;
         const int most = emph_conv_stack_max_layers();
         const int groups = (total + most - 1) / most;
         float* buffers[2] = {current, other};
@@ -109,15 +113,21 @@ int emph_prominence_forward(const emph_conv_model* model, const void* audio,
             const int size = (total - done + (groups - group) - 1) / (groups - group);
             int relu = 0;
             for (int l = 0; l < size; ++l)
-                if (done + l >= 1 && m.activation == EMPH_ACT_RELU) relu |= 1 << l;
+                if (done + l + skip >= 1 && m.activation == EMPH_ACT_RELU) relu |= 1 << l;
             // the closing group leaves running sums when the per-word sum is folded
             const bool to_sums = group == groups - 1 && fold;
             float* out = to_sums ? sums : buffers[group & 1];
-            status = emph_conv1d_stack(in, ld_frames, out, to_sums ? c : ld_frames,
-                                       m.input_pack + done * pack_floats,
-                                       m.input_bias + static_cast<int64_t>(done) * c, size, relu,
-                                       conv_spans, n_conv_spans,
-                                       to_sums ? word_sums->slot_map : nullptr, stream);
+            // (packs and biases of the model's layers, input layer first)
+            const float* packs = m.input_pack + (done + skip) * pack_floats;
+            const float* biases = m.input_bias + static_cast<int64_t>(done + skip) * c;
+            status = composed && group == 0
+                         ? emph_conv1d_stack_composed(
+                               in, ld_frames, out, to_sums ? c : ld_frames, m.compose,
+                               packs + pack_floats, biases + c, size, relu, conv_spans,
+                               n_conv_spans, to_sums ? word_sums->slot_map : nullptr, stream)
+                         : emph_conv1d_stack(in, ld_frames, out, to_sums ? c : ld_frames, packs,
+                                             biases, size, relu, conv_spans, n_conv_spans,
+                                             to_sums ? word_sums->slot_map : nullptr, stream);
             if (status) return status;
             in = out;
             done += size;

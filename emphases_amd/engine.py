@@ -315,6 +315,26 @@ class Engine:
         if self.split_conv:
             self._split_packs = to(np.concatenate(
                 [runtime.conv_split_pack(layer.weight) for layer in frame_stack]))
+        # the input layer has no activation (model/core.py:17-31,92-100): it and
+        # the first encoder layer are one 5-tap layer, F(4,5), in the first
+        # launch (emph_conv1d_stack_composed) - one allocation per checkpoint.
+        # EMPHASES_CONV_COMPOSE=0: the two F(4,3) layers.  Only in front of a
+        # per-word sum or average: outputs 0 and 3 of an F(4,5) quad carry
+        # about twice the rounding error of F(4,3)'s, which a sum over a
+        # word's frames averages out and 'max' / 'center' - one frame per word
+        # and channel - hand on as it is (conv_max against float64: 3.4e-6 x
+        # scale composed, where the opt-in precisions promise 3e-6)
+        self.compose = bool(
+            self.stack and not self.split_conv and
+            len(self.frame_encoder) > 0 and
+            config.downsample_method in ('sum', 'average') and
+            os.environ.get('EMPHASES_CONV_COMPOSE', '1') != '0')
+        self._compose_pack = None
+        if self.compose:
+            first = self.frame_encoder[0]
+            self._compose_pack = to(runtime.conv_compose_pack(
+                self.input_layer.weight, self.input_layer.bias.cpu().numpy(),
+                first.weight, first.bias.cpu().numpy()))
         self.model = self._conv_model()
 
     def lane(self):
@@ -376,7 +396,8 @@ class Engine:
             decoder_packs=pointer(self.decoder_packs),
             decoder_biases=pointer(self.decoder_biases),
             out_weight=pointer(self.output_weight),
-            out_bias=pointer(self.output_bias))
+            out_bias=pointer(self.output_bias),
+            compose=pointer(self._compose_pack if self.stack else None))
 
     def _stack(self, prefix):
         config, state, dev = self.config, self.state, self.device
@@ -1061,7 +1082,10 @@ class Engine:
         config = self.config
         channels = config.channels
         spans, span_size = meta['conv_spans']
-        total = 1 + len(self.frame_encoder)
+        # composed: the input layer and encoder layer 0 are the first launch's
+        # first (5-tap) layer - one effective layer less
+        skip = int(self.compose)
+        total = 1 + len(self.frame_encoder) - skip
         most = int(self.lib.emph_conv_stack_max_layers())
         groups = -(-total // most)
         fold = 'word_sum_tables' in meta
@@ -1078,10 +1102,11 @@ class Engine:
         for group in range(groups if frames else 0):
             size = -(-(total - done) // (groups - group))
             relu = sum(1 << l for l in range(size)
-                       if done + l >= 1 and relu_layers)
+                       if done + l + skip >= 1 and relu_layers)
             to_sums = fold and group == groups - 1
             target = sums if to_sums else buffers[group & 1]
-            flops = 2. * 80 * 80 * 3 * plan.total_frames * size
+            flops = 2. * 80 * 80 * 3 * plan.total_frames * (
+                size + (skip if group == 0 else 0))
             if self.split_conv:
                 with self._timed('conv1d_split_frames_80x80_k3', flops):
                     runtime.check(self.lib.emph_conv1d_split(
@@ -1095,15 +1120,29 @@ class Engine:
                 source = target
                 done += size
                 continue
+            layer = done + skip          # the model's layer, input layer first
             with self._timed('conv1d_stack_frames_80x80_k3', flops):
-                runtime.check(self.lib.emph_conv1d_stack(
-                    source.data_ptr(), ld_f, target.data_ptr(),
-                    channels if to_sums else ld_f,
-                    self._stack_packs[done * pack:].data_ptr(),
-                    self._stack_biases[done * channels:].data_ptr(), size,
-                    relu, spans.data_ptr(), span_size // 8,
-                    view('slot_map').data_ptr() if to_sums else None,
-                    runtime.stream()), 'emph_conv1d_stack')
+                if self.compose and group == 0:
+                    runtime.check(self.lib.emph_conv1d_stack_composed(
+                        source.data_ptr(), ld_f, target.data_ptr(),
+                        channels if to_sums else ld_f,
+                        self._compose_pack.data_ptr(),
+                        self._stack_packs[(layer + 1) * pack:].data_ptr()
+                        if size > 1 else None,
+                        self._stack_biases[(layer + 1) * channels:].data_ptr()
+                        if size > 1 else None, size,
+                        relu, spans.data_ptr(), span_size // 8,
+                        view('slot_map').data_ptr() if to_sums else None,
+                        runtime.stream()), 'emph_conv1d_stack_composed')
+                else:
+                    runtime.check(self.lib.emph_conv1d_stack(
+                        source.data_ptr(), ld_f, target.data_ptr(),
+                        channels if to_sums else ld_f,
+                        self._stack_packs[layer * pack:].data_ptr(),
+                        self._stack_biases[layer * channels:].data_ptr(),
+                        size, relu, spans.data_ptr(), span_size // 8,
+                        view('slot_map').data_ptr() if to_sums else None,
+                        runtime.stream()), 'emph_conv1d_stack')
             source = target
             done += size
         if not words:

@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -89,6 +89,11 @@ SIGNATURES = {
     'emph_conv1d_stack': (_c.c_int, [
         _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i32, _i32, _ptr, _i32, _ptr,
         _ptr]),
+    'emph_conv_compose_pack_size': (_i64, []),
+    'emph_conv_compose_pack': (_c.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr]),
+    'emph_conv1d_stack_composed': (_c.c_int, [
+        _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i32, _i32, _ptr, _i32,
+        _ptr, _ptr]),
     'emph_conv_split_pack_size': (_i64, []),
     'emph_conv_split_pack': (_c.c_int, [_ptr, _ptr]),
     'emph_conv1d_split': (_c.c_int, [
@@ -416,7 +421,8 @@ class ConvModel(_c.Structure):
         'normalize', 'mel_nnz', 'conv_variant')] + [(name, _ptr) for name in (
             'table', 'mel_start', 'mel_count', 'mel_offset', 'mel_values',
             'input_pack', 'input_bias', 'encoder_packs', 'encoder_biases',
-            'decoder_packs', 'decoder_biases', 'out_weight', 'out_bias')]
+            'decoder_packs', 'decoder_biases', 'out_weight', 'out_bias',
+            'compose')]
 
 
 class WordSumTables(_c.Structure):
@@ -437,6 +443,23 @@ def word_decoder_pack(weight):
     check(lib.emph_word_decoder_pack(
         weight.ctypes.data, channels, kernel_size, pack.ctypes.data),
         'emph_word_decoder_pack')
+    return pack
+
+
+def conv_compose_pack(w0, b0, w1, b1):
+    """`emph_conv_compose_pack`: two Conv1d(80, 80, 3, 'same') layers with no
+    activation between them as one 5-tap layer - its F(4,5) pack, its bias and
+    the edge terms that restore the intermediate's zero padding (host, numpy
+    float32)."""
+    lib = library()
+    arrays = [np.ascontiguousarray(a, dtype=np.float32)
+              for a in (w0, b0, w1, b1)]
+    assert arrays[0].shape == arrays[2].shape == (80, 80, 3)
+    assert arrays[1].shape == arrays[3].shape == (80,)
+    pack = np.zeros(lib.emph_conv_compose_pack_size(), dtype=np.float32)
+    check(lib.emph_conv_compose_pack(
+        *[a.ctypes.data for a in arrays], pack.ctypes.data),
+        'emph_conv_compose_pack')
     return pack
 
 

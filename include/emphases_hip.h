@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 38
+#define EMPH_ABI_VERSION 39
 
 /* Segment-table fields */
 enum {
@@ -450,6 +450,37 @@ int emph_conv1d_stack(const float* x, int64_t ldx, float* y, int64_t ldy,
                       const float* packs, const float* biases, int32_t layers,
                       int32_t relu_mask, const int32_t* spans, int32_t n_spans,
                       const int32_t* slot_map, void* stream);
+
+/* The input layer and the first encoder layer as ONE layer: the model applies
+ * frame_encoder(input_layer(x)) (emphases/model/core.py:17-31,92-100) and the
+ * input layer is a bare Conv1d(80, 80, 3, 'same') with no activation, so the
+ * two ATen convolutions in a row are one 5-tap convolution
+ *   Wc[d] = sum_{a + c = d} W1[a] W0[c],  bc = b1 + (sum_a W1[a]) b0
+ * - Winograd F(4,5), 8 multiplies per 4 outputs where two F(4,3) layers take
+ * 12 - except at a segment's first and last position, where 'same' padding
+ * zeroes the intermediate:
+ *   y1[0]     = z[0]     - W1[0] (b0 + W0[2] x[0])
+ *   y1[n - 1] = z[n - 1] - W1[2] (b0 + W0[0] x[n - 1])
+ * emph_conv_compose_pack forms Wc, bc, the F(4,5) filter transform (points 0,
+ * +-1, +-2, +-1/2, inf) and the four edge terms in float64 from the float32
+ * host arrays w0, w1 [80][80][3] and b0, b1 [80], once per checkpoint:
+ * emph_conv_compose_pack_size() floats, k-major like emph_conv_winograd4_pack
+ * (per k-step 8 x 5 m-tiles x 64 lanes), then bc, E_L^T, e_L, E_R^T, e_R.
+ * emph_conv1d_stack_composed is emph_conv1d_stack whose first layer is that
+ * layer (`compose`: the pack's device copy, 16-byte aligned): `layers`
+ * (1 .. 3) counts it, bit 0 of `relu_mask` is the first encoder layer's
+ * activation, `packs` / `biases` hold the layers - 1 F(4,3) layers behind it.
+ * Same spans, same `slot_map` contract.  Against the two layers it replaces
+ * the values differ by rounding only (another, equally accurate, sum). */
+int64_t emph_conv_compose_pack_size(void);
+int emph_conv_compose_pack(const float* w0, const float* b0, const float* w1,
+                           const float* b1, float* host_pack);
+int emph_conv1d_stack_composed(const float* x, int64_t ldx, float* y,
+                               int64_t ldy, const float* compose,
+                               const float* packs, const float* biases,
+                               int32_t layers, int32_t relu_mask,
+                               const int32_t* spans, int32_t n_spans,
+                               const int32_t* slot_map, void* stream);
 
 /* The same group of layers on the bf16 matrix pipe, direct form, every fp32
  * operand split into two bf16 pieces (three products per term, fp32
@@ -1034,6 +1065,9 @@ typedef struct emph_conv_model {
     const float* decoder_biases;  /* [decoder_layers][C]                       */
     const float* out_weight;      /* [1][C][decoder_kernel_size]               */
     const float* out_bias;        /* [1]                                       */
+    const float* compose;         /* emph_conv_compose_pack of the input layer and
+                                     encoder layer 0, or NULL: the conv-span path
+                                     then runs them as one layer                */
 } emph_conv_model;
 
 /* Tables of the fused per-word sum (emph_conv1d_winograd4_word_sums +
@@ -1067,7 +1101,9 @@ int64_t emph_prominence_workspace_floats(int32_t features, int32_t channels,
  * as groups of up to three layers per launch (emph_conv1d_stack) when the model
  * is the 80 -> 80 family with `input_pack` / `encoder_packs` and `input_bias`
  * / `encoder_biases` back to back in memory; `word_sums` must then follow the
- * spans' restarts.  Enqueues on `stream`; allocates nothing. */
+ * spans' restarts.  With `model->compose` set (and at least one encoder
+ * layer) the first launch is emph_conv1d_stack_composed and the groups are
+ * formed over one layer less.  Enqueues on `stream`; allocates nothing. */
 int emph_prominence_forward(const emph_conv_model* model, const void* audio,
                             int32_t audio_format, const int64_t* seg,
                             const int32_t* frontend_tiles,

@@ -1,5 +1,6 @@
 // Standalone micro-benchmark of emph_conv1d_stack on the configs[1] layout (64 x 1000
-// frames = 256 spans), against the same layers as emph_conv1d_winograd4 launches.
+// frames = 256 spans), against the same layers as emph_conv1d_winograd4 launches and against
+// emph_conv1d_stack_composed (the 5-tap first layer).  usage: stack_bench [layers [composed]]
 // Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -Iinclude -Iemphases_amd/csrc \
 //            tools/micro/stack_bench.hip emphases_amd/csrc/frontend.hip -o tools/micro/bin/stack_bench
 //        (frontend.hip supplies set_error; -DSTACK_STAMPS adds the in-kernel timeline)
@@ -99,12 +100,32 @@ int main(int argc, char** argv) {
     };
     time("emph_conv1d_stack", stack);
     time("emph_conv1d_winograd4 x L", layered);
+    // the same launch with the composed 5-tap layer (layers 0 and 1 of the weights as one) in
+    // front of its layers - 1 F(4,3) layers: one model layer more than the launch above
+    std::vector<float> hc(static_cast<size_t>(emph_conv_compose_pack_size()));
+    if (emph_conv_compose_pack(hw.data(), hb.data(), hw.data() + (layers > 1 ? c * c * 3 : 0), hb.data(), hc.data())) {
+        printf("compose pack failed: %s\n", emph_last_error());
+        return 1;
+    }
+    float* compose;
+    CHECK(hipMalloc(&compose, hc.size() * 4));
+    CHECK(hipMemcpy(compose, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
+    auto composed = [&] {
+        if (emph_conv1d_stack_composed(x, ld, y, ld, compose, packs, biases, layers, relu | 1, spans, n_spans,
+                                       nullptr, nullptr)) {
+            printf("composed stack failed: %s\n", emph_last_error());
+            exit(1);
+        }
+    };
+    time("emph_conv1d_stack_composed", composed);
 #ifdef STACK_STAMPS
     unsigned long long* stamps;
     const size_t count = static_cast<size_t>(n_spans) * 12 * 32;
     CHECK(hipMalloc(&stamps, 2 * count * 8)); CHECK(hipMemset(stamps, 0, 2 * count * 8));
     CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stack_stamps), &stamps, sizeof(stamps)));
-    stack(); CHECK(hipDeviceSynchronize());
+    // (a second argument: the timeline of the composed launch)
+    if (argc > 2) composed(); else stack();
+    CHECK(hipDeviceSynchronize());
     std::vector<unsigned long long> hs2(2 * count);
     CHECK(hipMemcpy(hs2.data(), stamps, 2 * count * 8, hipMemcpyDeviceToHost));
     unsigned long long first = ~0ull;
