@@ -2,7 +2,7 @@
 
 The drop-in surface mirrors `import emphases` of the reference for its
 inference hot path: `from_alignment_and_audio`, `from_file(s)_to_file(s)`,
-the step functions `preprocess` / `infer` / `postprocess` / `downsample` and
+the step functions `preprocess` / `infer` / `postprocess` / `downsample` / `upsample` and
 `Model`; the hot path itself runs in libemphases_hip.so (include/emphases_hip.h).
 """
 from .config import *  # noqa: F401,F403  (SAMPLE_RATE, HOPSIZE, Config, ...)
@@ -23,7 +23,7 @@ from .core import (  # noqa: F401
     Model, active_config, configure, downsample, from_alignment_and_audio,
     from_alignments_and_audios, from_file, from_file_to_file,
     from_files_to_files, from_text_and_audio, get_engine, get_session, infer,
-    inference_context, postprocess, preprocess, resample, segment)
+    inference_context, postprocess, preprocess, resample, segment, upsample)
 # the paper's baselines behind Config.method (emphases.baselines.*)
 from . import baselines  # noqa: F401,E402
 # dataset evaluation (emphases.evaluate.{datasets, Metrics, metrics})

@@ -39,6 +39,8 @@ ARCHITECTURES = ('convolution', 'transformer')
 DOWNSAMPLE_LOCATIONS = ('input', 'intermediate', 'inference', 'loss')
 DOWNSAMPLE_METHODS = ('sum', 'average', 'max', 'center')
 LOSSES = ('bce', 'mse')
+# Word -> frame interpolation of the targets (defaults.py:213-215)
+UPSAMPLE_METHODS = ('linear', 'nearest')
 # Emphasis annotation methods (defaults.py:211, dispatch core.py:244-287)
 METHODS = ('neural', 'pitch-variance', 'duration-variance', 'prominence')
 
@@ -73,6 +75,9 @@ class Config:
     # Emphasis annotation method (defaults.py:211): the model, or one of the
     # paper's baselines (`baselines/`), which build no model at all
     method: str = 'neural'
+    # Word -> frame interpolation (defaults.py:213-215): `upsample`, and the
+    # frame-rate targets of training at downsample_location 'inference'
+    upsample_method: str = 'linear'
 
     def __post_init__(self):
         if self.method not in METHODS:
@@ -94,6 +99,11 @@ class Config:
             # core.py:468-469
             raise ValueError(
                 f'Interpolation method {self.downsample_method} '
+                'is not defined')
+        if self.upsample_method not in UPSAMPLE_METHODS:
+            # core.py:539-542
+            raise ValueError(
+                f'Interpolation method {self.upsample_method} '
                 'is not defined')
         if self.loss not in LOSSES:
             raise ValueError(f'Loss {self.loss} is not defined')

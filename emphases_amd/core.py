@@ -516,6 +516,79 @@ def downsample(xs, word_bounds, word_lengths, config=None):
     return result if xs.is_cuda else result.cpu()
 
 
+def upsample(xs, word_bounds, word_lengths, frame_lengths, config=None):
+    """Interpolate from word to frame resolution (`core.py:472-544`): xs
+    [B, C, W], word_bounds [B, 2, W], word_lengths [B], frame_lengths [B] ->
+    [B, C, max frames], zero behind an item's frames.  With the word centres
+    c_w = start + (end - start) / 2 and the frame centres t + 0.5,
+    `config.upsample_method` 'nearest' takes the last word whose centre is not
+    to the right of the frame (the first word in front of it), 'linear' the
+    line through that word and the next, extrapolated at both ends and not
+    clamped; an item of one word is that word's value everywhere.  One
+    `emph_upsample` launch.
+
+    Two deviations from the reference:
+
+    * the words of an item must be sorted, disjoint and non-empty, and every
+      item needs one: ValueError otherwise (two equal centres divide by zero
+      in the reference);
+    * under 'linear' every channel is interpolated on its own.  The reference
+      indexes every channel's line with row 0 (its `line_idx` is all zeros,
+      `core.py:514-519`): all rows come back as copies of row 0; so does its
+      one-word branch, which writes `x[0]`, channel 0, to every channel
+      (`core.py:494-495`).  Targets have one channel, where the two agree."""
+    config = config or active_config()
+    device = runtime.require_gpu(xs.device if xs.is_cuda else None)
+    lib = runtime.library()
+    frames = [int(n) for n in frame_lengths]
+    lengths = [int(n) for n in word_lengths]
+    if xs.dim() != 3 or word_bounds.dim() != 3 or word_bounds.shape[1] != 2 \
+            or not len(frames) == len(lengths) == xs.shape[0] == \
+            word_bounds.shape[0]:
+        raise ValueError(
+            'upsample takes xs [B, C, W], word_bounds [B, 2, W] and B lengths')
+    bounds = np.asarray(word_bounds.cpu(), dtype=np.int64)
+    for index, (count, length) in enumerate(zip(frames, lengths)):
+        if count < 1:
+            raise ValueError(f'item {index}: no frame')
+        if not 1 <= length <= min(bounds.shape[2], xs.shape[2]):
+            raise ValueError(
+                f'item {index}: word length {length} outside 1..'
+                f'{min(bounds.shape[2], xs.shape[2])}')
+        starts, ends = bounds[index, 0, :length], bounds[index, 1, :length]
+        if np.any(ends <= starts):
+            raise ValueError(f'item {index}: a word with end <= start')
+        if np.any(starts[1:] < ends[:-1]):
+            raise ValueError(
+                f'item {index}: words overlap or are not in order')
+    plan = _packed_plan(frames, torch.from_numpy(bounds), lengths)
+    tile_request = (runtime.AXIS_FRAMES, 64)
+    with torch.cuda.device(device):
+        host, offsets = plan.pack_metadata([tile_request])
+        meta = torch.from_numpy(host).to(device)
+        view = lambda name: meta[  # noqa: E731
+            offsets[name][0]:offsets[name][0] + offsets[name][1]]
+        tiles = view(('tiles',) + tile_request)
+        packed = _pack(
+            xs.to(device, torch.float32), plan, plan.word_off, plan.words,
+            plan.ld_words, device)
+        out = torch.zeros(
+            (xs.shape[1], plan.ld_frames), dtype=torch.float32, device=device)
+        runtime.check(lib.emph_upsample(
+            packed.data_ptr(), plan.ld_words, view('bounds').data_ptr(),
+            out.data_ptr(), plan.ld_frames, xs.shape[1],
+            view('table').data_ptr(), tiles.data_ptr(),
+            tiles.numel() // runtime.TILE_FIELDS,
+            runtime.UPSAMPLE_METHODS[config.upsample_method],
+            runtime.stream()), 'emph_upsample')
+        result = torch.zeros(
+            (xs.shape[0], xs.shape[1], max(frames) if frames else 0),
+            dtype=torch.float32, device=device)
+        for index, (off, count) in enumerate(zip(plan.frame_off, plan.frames)):
+            result[index, :, :count] = out[:, off:off + count]
+    return result if xs.is_cuda else result.cpu()
+
+
 def segment(xs, word_bounds, word_lengths):
     """Convert acoustic features to word segments (`core.py:552-586`): xs
     [B, C, T], word_bounds [B, 2, W], word_lengths [B] -> (segments

@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -31,6 +31,7 @@ REDUCTIONS = {'sum': 0, 'average': 1, 'max': 2, 'center': 3}
 POSTPROCESS = {None: 0, 'bce': 1, 'mse': 2}
 # BCE forms of emph_word_metrics_grouped, by LOSS
 BCE_FORMS = {'bce': 0, 'mse': 1}
+UPSAMPLE_METHODS = {'linear': 0, 'nearest': 1}
 AUDIO_F32, AUDIO_PCM16 = 0, 1
 SPREAD_IDENTITY, SPREAD_LOG2 = 0, 1
 (METRIC_COUNT, METRIC_BCE, METRIC_SQUARED_ERROR, METRIC_COVARIANCE,
@@ -230,6 +231,17 @@ SIGNATURES = {
         _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _ptr,
         _i32, _i32, _ptr]),
     'emph_activation_gradient': (_c.c_int, [_ptr, _ptr, _i64, _i32, _ptr]),
+    'emph_upsample': (_c.c_int, [
+        _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _i32, _i32, _ptr]),
+    'emph_frame_head': (_c.c_int, [
+        _ptr, _i64, _ptr, _ptr, _i32, _i32, _ptr, _i32, _ptr, _ptr]),
+    'emph_frame_loss_grad': (_c.c_int, [
+        _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _i32, _i64, _i32, _i32, _ptr,
+        _ptr, _ptr, _ptr]),
+    'emph_frame_head_parts': (_i32, [_i32]),
+    'emph_frame_head_backward': (_c.c_int, [
+        _ptr, _ptr, _i64, _ptr, _i32, _i32, _ptr, _i32, _ptr, _ptr, _ptr,
+        _ptr, _i64, _ptr]),
     'emph_adam_step': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _i64, _c.c_double, _c.c_double, _f32, _f32,
         _f32, _ptr]),

@@ -3,12 +3,13 @@ forward with every layer kept, masked loss, backward and Adam
 (`emphases/train/core.py:91-142`) - and the loop around it - resume, train,
 validate, save (`train/core.py:13-307`) - fed by `emphases_amd.data`; and
 `TorchModel`, the same architecture as a `torch.nn.Module` on the
-differentiable operator seams for the configurations the fused step refuses."""
+differentiable operator seams for the configurations the fused steps refuse.
+`EncoderTrainer` is the step of the models without a word decoder
+(downsample_location 'inference' and 'loss'); `make_trainer` picks the class."""
 from .core import (  # noqa: F401
-    PRECISIONS, Batch, Trainer, adam_state_dict, check_batch,
-    check_precision, check_supported, checkpoint_names, gather_tables,
-    initial_state,
-    layer_names, parameter_offsets, split_layer_names, split_pack_tables,
+    PRECISIONS, Batch, EncoderTrainer, Trainer, adam_state_dict, check_batch,
+    check_encoder_supported, check_precision, check_supported,
+    checkpoint_names, gather_tables, initial_state, layer_names, make_trainer, parameter_offsets, split_layer_names, split_pack_tables,
     write_checkpoint)
 from . import dropout  # noqa: F401
 from .model import (  # noqa: F401

@@ -40,8 +40,20 @@ def parse_args(arguments=None):
         '--loss', choices=emphases_amd.config.LOSSES,
         help="The loss: 'bce' (default) or 'mse'")
     parser.add_argument(
-        '--downsample_method', choices=('sum', 'average'),
-        help="The word reduction: 'sum' (default) or 'average'")
+        '--downsample_method', choices=emphases_amd.config.DOWNSAMPLE_METHODS,
+        help="The word reduction: 'sum' (default), 'average', 'max' or "
+             "'center' (the last two at --downsample_location inference or "
+             'loss only)')
+    parser.add_argument(
+        '--downsample_location',
+        choices=('intermediate', 'inference', 'loss'),
+        help="Where the frames become words: 'intermediate' (default, with "
+             "a word decoder), 'inference' (frame-rate loss against "
+             "upsampled targets) or 'loss' (word-rate loss, no decoder)")
+    parser.add_argument(
+        '--upsample_method', choices=emphases_amd.config.UPSAMPLE_METHODS,
+        help="The interpolation of the targets at --downsample_location "
+             "inference: 'linear' (default) or 'nearest'")
     parser.add_argument(
         '--dropout', type=float,
         help='Dropout probability after every activation of the conv stacks '
@@ -57,7 +69,8 @@ def main(arguments=None):
     arguments = vars(parse_args(arguments))
     overrides = {
         name: arguments.pop(name)
-        for name in ('loss', 'downsample_method', 'dropout')}
+        for name in ('loss', 'downsample_method', 'downsample_location',
+                     'upsample_method', 'dropout')}
     overrides = {
         name: value for name, value in overrides.items() if value is not None}
     if overrides:

@@ -24,6 +24,16 @@ library on one stream.  Deliberate, documented deviations:
   (`model/layers/convolution.py:35-37` ignores lengths).  The loss is the mean
   over all valid words of the batch, as the reference's masked loss is.
 
+`EncoderTrainer` is the same step for the models without a word decoder
+(`DOWNSAMPLE_LOCATION` 'inference' and 'loss', `model/core.py:28-30,109-138`):
+the frame encoder goes straight to `output_layer`, at word rate behind the
+reduce for 'loss', at frame rate against targets that `emphases.upsample`
+spreads over the frames for 'inference' (`train/core.py:324-353`).  It keeps
+`Trainer`'s semantics: every utterance is trained alone, with its own zero
+halo; the 'inference' loss is the mean over all frames of the batch, the
+'loss' loss the mean over all words; the output layer, the loss and Adam
+stay float32 at either precision.
+
 All parameters live in ONE flat device buffer in `weights.parameter_shapes`
 order (the order of `Model.parameters()`); gradients and the two Adam moments
 are buffers of the same shape.  The MFMA weight packs of the forward kernel
@@ -84,6 +94,44 @@ def check_supported(config):
         refuse('mel_feature', 'True (80..83 input features)')
 
 
+def check_encoder_supported(config):
+    """`check_supported` for `EncoderTrainer`: the models without a word
+    decoder, downsample_location 'inference' or 'loss'."""
+    def refuse(field, supported):
+        raise NotImplementedError(
+            f'the encoder training step supports {field} {supported} only, '
+            f'not {field}={getattr(config, field)!r}')
+    if config.method != 'neural':
+        refuse('method', "'neural'")
+    if config.architecture != 'convolution':
+        refuse('architecture', "'convolution'")
+    if config.downsample_location not in ('inference', 'loss'):
+        refuse('downsample_location', "'inference' or 'loss'")
+    if config.activation != 'relu':
+        refuse('activation', "'relu'")
+    if config.loss not in ('bce', 'mse'):
+        refuse('loss', "'bce' or 'mse'")
+    if config.channels != 80:
+        refuse('channels', '80')
+    if config.encoder_kernel_size != 3:
+        refuse('encoder_kernel_size', '3')
+    if config.decoder_kernel_size != 3:
+        refuse('decoder_kernel_size', "3 (the output layer's kernel size)")
+    if not 0 <= config.layers <= 16:
+        refuse('layers', '0..16')
+    if not config.mel_feature:
+        refuse('mel_feature', 'True (80..83 input features)')
+
+
+def _check_step(config):
+    """The check of the step that trains `config`: `Trainer`'s with a word
+    decoder, `EncoderTrainer`'s without."""
+    if config.has_decoder:
+        check_supported(config)
+    else:
+        check_encoder_supported(config)
+
+
 def check_precision(precision):
     """'f32' or 'bf16x3'; NotImplementedError for the inference precisions the
     step does not cover, ValueError for anything else - before a GPU is
@@ -112,9 +160,12 @@ def split_layer_names(config):
 
 
 def layer_names(config):
-    """The Conv1d(., 80, 3) layers in forward order."""
+    """The Conv1d(., 80, 3) layers in forward order (no word decoder at
+    downsample_location 'inference' and 'loss', `model/core.py:28-30`)."""
+    prefixes = ('frame_encoder', 'word_decoder') if config.has_decoder else \
+        ('frame_encoder',)
     return ['input_layer'] + [
-        f'{prefix}.{2 * i}' for prefix in ('frame_encoder', 'word_decoder')
+        f'{prefix}.{2 * i}' for prefix in prefixes
         for i in range(config.layers)]
 
 
@@ -151,7 +202,7 @@ def initial_state(config=cfg.DEFAULT, seed=0):
     the reference's construction order (`model/core.py:16-37`,
     `model/layers/convolution.py:22-33`).  The caller's generator is left
     as it was."""
-    check_supported(config)
+    _check_step(config)
     state = collections.OrderedDict()
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
@@ -166,6 +217,8 @@ def initial_state(config=cfg.DEFAULT, seed=0):
         for prefix, kernel_size in (
                 ('frame_encoder', config.encoder_kernel_size),
                 ('word_decoder', config.decoder_kernel_size)):
+            if prefix == 'word_decoder' and not config.has_decoder:
+                continue
             for i in range(config.layers):
                 conv(f'{prefix}.{2 * i}', config.channels, config.channels,
                      kernel_size)
@@ -189,7 +242,7 @@ def gather_tables(config=cfg.DEFAULT):
     packs (every layer) and of the data-gradient packs
     W'[ci][co][j] = W[co][ci][k - 1 - j] (every layer but the input layer,
     whose input needs no gradient)."""
-    check_supported(config)
+    _check_step(config)
     offsets, _ = parameter_offsets(config)
     pieces, forward, backward = [], {}, {}
     cursor = 0
@@ -220,7 +273,7 @@ def split_pack_tables(config=cfg.DEFAULT):
     e of a pack is weight [32 m + lane % 32][16 block + 8 (lane / 32) + e]
     [tap] of its layer, -1 (zeros) for rows 80 .. 95: the layout of
     `emph_conv_split_pack`."""
-    check_supported(config)
+    _check_step(config)
     offsets, _ = parameter_offsets(config)
     tap, block, m, lane, e = np.meshgrid(
         np.arange(3), np.arange(5), np.arange(3), np.arange(64), np.arange(8),
@@ -336,10 +389,15 @@ class Batch:
         self.targets = targets
 
 
-class Trainer:
-    """`Trainer(...).step(*batch[:5])` is one iteration of the reference's loop
-    (`train/core.py:105-142`) for the convolution model; see the module
-    docstring for the two deviations."""
+class _Step:
+    """What `Trainer` and `EncoderTrainer` share: the flat state, the batch
+    layout, the frame encoder's launches, Adam and the checkpoint.  A
+    subclass names its `_check` and gives `_buffers`, `_forward` (whose
+    buffers' 'logits' then hold the packed word logits) and
+    `_forward_backward` (which leaves the loss in `self.loss` and every
+    gradient in `self.gradients`)."""
+
+    _check = staticmethod(check_supported)
 
     def __init__(self, config=None, checkpoint=None, gpu=None, lr=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, seed=0, precision='f32'):
@@ -352,7 +410,7 @@ class Trainer:
         state dict, or a file `weights.load` reads; a file written by `save`
         also restores the Adam moments and the step count."""
         self.config = config = config or api.active_config()
-        check_supported(config)
+        self._check(config)
         self.precision = check_precision(precision)
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
         self.steps = 0
@@ -450,7 +508,8 @@ class Trainer:
     def save(self, path, epoch=0, step=None, score=0., best=0.):
         """The file `torchutil.checkpoint.save` writes in the reference's loop
         (`train/core.py:162-169,189-196`): every inference entry point takes it
-        as `checkpoint=`, `Trainer(checkpoint=path)` resumes from it."""
+        as `checkpoint=`, the same class with `checkpoint=path` resumes from
+        it."""
         write_checkpoint(
             path, self.state_dict(), self.optimizer_state_dict(), epoch,
             self.steps if step is None else step, score, best)
@@ -525,33 +584,6 @@ class Trainer:
             return arguments[0]
         return self.prepare(*arguments)
 
-    def _buffers(self, plan):
-        """The activations and gradients of a step for a packed layout, kept
-        between steps (zero at first, so that padding columns stay finite)."""
-        frame_tiles = len(plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
-        word_tiles = len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE))
-        parts = max(
-            int(self.lib.emph_conv_weight_grad_parts(n))
-            for n in (frame_tiles, word_tiles))
-        key = (plan.ld_frames, plan.ld_words, parts)
-        found = self._workspace.get(key)
-        if found is None:
-            self._workspace.clear()
-            channels, layers = self.config.channels, self.config.layers
-            zeros = lambda *shape: torch.zeros(  # noqa: E731
-                shape, dtype=torch.float32, device=self.device)
-            slab = channels * 3 * self.config.num_features + channels
-            found = {
-                'frames': zeros(layers + 1, channels, plan.ld_frames),
-                'words': zeros(layers + 1, channels, plan.ld_words),
-                'frame_grad': zeros(2, channels, plan.ld_frames),
-                'word_grad': zeros(2, channels, plan.ld_words),
-                'logits': zeros(plan.ld_words),
-                'dlogit': zeros(plan.ld_words),
-                'slabs': zeros(max(parts, 1) * slab)}
-            self._workspace[key] = found
-        return found
-
     ###########################################################################
     # Launches
     ###########################################################################
@@ -612,122 +644,62 @@ class Trainer:
             dropout_module.stream_of(self.config, name), self.steps,
             runtime.stream()), 'emph_dropout')
 
-    def _forward(self, batch, training=False):
-        """The forward launches of a step; returns the step's buffers, whose
-        'logits' then hold the packed logits [ld_words].  `training`: with
-        the dropout masks of the step (never for validation)."""
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        ld_f, ld_w = plan.ld_frames, plan.ld_words
-        frames, words = runtime.AXIS_FRAMES, runtime.AXIS_WORDS
-        buffers = self._buffers(plan)
-        stream = runtime.stream()
-        drop = training and self.dropout > 0.
-        word_tiles = meta[('tiles', words, WORD_TILE)]
-        table, bounds = meta['table'], meta['bounds']
-        word_segment = meta['word_segment']
-        mode = runtime.REDUCTIONS[config.downsample_method]
-        encoder = [f'frame_encoder.{2 * i}' for i in range(layers)]
-        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
-
-        # ---- forward, every layer's output kept (model/core.py:91-107,138)
-        h, d = buffers['frames'], buffers['words']
+    def _encoder_forward(self, batch, h, drop):
+        """input_layer and the frame encoder (model/core.py:91-94), every
+        layer's output kept: h[0] .. h[layers]."""
+        config, ld_f = self.config, batch.plan.ld_frames
         self._frame_conv('input_layer', batch.features, h[0], ld_f,
                          config.num_features, None, batch)
-        for i, name in enumerate(encoder):
-            self._frame_conv(name, h[i], h[i + 1], ld_f, channels, 'relu',
-                             batch)
+        for i in range(config.layers):
+            name = f'frame_encoder.{2 * i}'
+            self._frame_conv(name, h[i], h[i + 1], ld_f, config.channels,
+                             'relu', batch)
             if drop:
                 self._dropout(name, h[i + 1])
-        runtime.check(lib.emph_segment_reduce(
-            h[layers].data_ptr(), ld_f, bounds.data_ptr(), d[0].data_ptr(),
-            ld_w, channels, table.data_ptr(), word_segment.data_ptr(), ld_w,
-            mode, stream), 'emph_segment_reduce')
-        for i, name in enumerate(decoder):
-            self._conv(self._forward_packs[name],
-                       self._parameter(f'{name}.bias'), d[i], d[i + 1], ld_w,
-                       channels, 'relu', word_tiles, WORD_TILE)
-            if drop:
-                self._dropout(name, d[i + 1])
-        logits = buffers['logits']
-        runtime.check(lib.emph_output_layer(
-            d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
-            self._parameter('output_layer.bias'), channels, 3,
-            table.data_ptr(), word_segment.data_ptr(), ld_w, words, 0,
-            logits.data_ptr(), None, stream), 'emph_output_layer')
-        return buffers
 
-    def _forward_backward(self, batch):
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        ld_f, ld_w = plan.ld_frames, plan.ld_words
-        buffers = self._forward(batch, training=True)
-        stream = runtime.stream()
-        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
-        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
-        word_grad_tiles = meta[('tiles', runtime.AXIS_WORDS, GRAD_TILE)]
-        table, bounds = meta['table'], meta['bounds']
-        word_segment = meta['word_segment']
-        mode = runtime.REDUCTIONS[config.downsample_method]
-        encoder = [f'frame_encoder.{2 * i}' for i in range(layers)]
-        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
-        h, d = buffers['frames'], buffers['words']
-        logits, dlogit = buffers['logits'], buffers['dlogit']
+    def _backward_stack(self, batch, buffers, names, outputs, gradient, ld,
+                        grad_tiles, tiles, tile):
+        """Backward of a conv stack, from the gradient of the last output
+        (gradient[0]) down to the gradient of outputs[0]; returns the buffer
+        that holds it."""
+        lib, channels, stream = self.lib, self.config.channels, runtime.stream()
+        current = 0
+        for i in range(len(names) - 1, -1, -1):
+            name = names[i]
+            dy = gradient[current]
+            if self.dropout > 0.:
+                runtime.check(lib.emph_activation_dropout_backward(
+                    outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
+                    runtime.ACTIVATIONS['relu'], self.dropout, stream),
+                    'emph_activation_dropout_backward')
+            else:
+                runtime.check(lib.emph_activation_backward(
+                    outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
+                    runtime.ACTIVATIONS['relu'], stream),
+                    'emph_activation_backward')
+            self._weight_grad(dy, outputs[i], ld, channels, name,
+                              grad_tiles, buffers)
+            if name in self._split_backward:
+                self._conv_split(
+                    self._split_backward[name],
+                    self._zero_bias.data_ptr(), dy, gradient[1 - current],
+                    ld, False, batch.meta['conv_spans'])
+            else:
+                self._conv(self._backward_packs[name], None, dy,
+                           gradient[1 - current], ld, channels, None,
+                           tiles, tile)
+            current = 1 - current
+        return gradient[current]
 
-        # ---- loss (train/core.py:315-353) and backward
-        runtime.check(lib.emph_loss_grad(
-            logits.data_ptr(), batch.targets.data_ptr(),
-            word_segment.data_ptr(), ld_w, plan.total_words,
-            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
-            dlogit.data_ptr(), stream), 'emph_loss_grad')
-        dd, dh = buffers['word_grad'], buffers['frame_grad']
-        runtime.check(lib.emph_output_layer_backward(
-            dlogit.data_ptr(), d[layers].data_ptr(), ld_w,
-            self._parameter('output_layer.weight'), word_segment.data_ptr(),
-            channels, 3, ld_w, self._gradient('output_layer.weight'),
-            self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
-            stream), 'emph_output_layer_backward')
-
-        def backward(names, outputs, gradient, ld, grad_tiles, tiles, tile):
-            """From the gradient of the last output (gradient[0]) down to the
-            gradient of outputs[0]; returns the buffer that holds it."""
-            current = 0
-            for i in range(len(names) - 1, -1, -1):
-                name = names[i]
-                dy = gradient[current]
-                if self.dropout > 0.:
-                    runtime.check(lib.emph_activation_dropout_backward(
-                        outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
-                        runtime.ACTIVATIONS['relu'], self.dropout, stream),
-                        'emph_activation_dropout_backward')
-                else:
-                    runtime.check(lib.emph_activation_backward(
-                        outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
-                        runtime.ACTIVATIONS['relu'], stream),
-                        'emph_activation_backward')
-                self._weight_grad(dy, outputs[i], ld, channels, name,
-                                  grad_tiles, buffers)
-                if name in self._split_backward:
-                    self._conv_split(
-                        self._split_backward[name],
-                        self._zero_bias.data_ptr(), dy, gradient[1 - current],
-                        ld, False, meta['conv_spans'])
-                else:
-                    self._conv(self._backward_packs[name], None, dy,
-                               gradient[1 - current], ld, channels, None,
-                               tiles, tile)
-                current = 1 - current
-            return gradient[current]
-
-        dword = backward(decoder, d, dd, ld_w, word_grad_tiles, word_tiles,
-                         WORD_TILE)
-        runtime.check(lib.emph_segment_broadcast(
-            dword.data_ptr(), ld_w, bounds.data_ptr(), dh[0].data_ptr(), ld_f,
-            channels, table.data_ptr(), frame_tiles.data_ptr(),
-            frame_tiles.numel() // runtime.TILE_FIELDS, mode, stream),
-            'emph_segment_broadcast')
-        dinput = backward(encoder, h, dh, ld_f, frame_tiles, frame_tiles,
-                          FRAME_TILE)
+    def _encoder_backward(self, batch, buffers):
+        """From the gradient of the encoder's output (buffers['frame_grad'][0])
+        to the gradients of the frame encoder and the input layer."""
+        config, ld_f = self.config, batch.plan.ld_frames
+        frame_tiles = batch.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        encoder = [f'frame_encoder.{2 * i}' for i in range(config.layers)]
+        dinput = self._backward_stack(
+            batch, buffers, encoder, buffers['frames'], buffers['frame_grad'],
+            ld_f, frame_tiles, frame_tiles, FRAME_TILE)
         self._weight_grad(dinput, batch.features, ld_f, config.num_features,
                           'input_layer', frame_tiles, buffers)
 
@@ -787,3 +759,266 @@ class Trainer:
                 'emph_adam_step')
             self._repack()
         return loss
+
+
+class Trainer(_Step):
+    """`Trainer(...).step(*batch[:5])` is one iteration of the reference's loop
+    (`train/core.py:105-142`) for the convolution model; see the module
+    docstring for the two deviations."""
+
+    def _buffers(self, plan):
+        """The activations and gradients of a step for a packed layout, kept
+        between steps (zero at first, so that padding columns stay finite)."""
+        frame_tiles = len(plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
+        word_tiles = len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE))
+        parts = max(
+            int(self.lib.emph_conv_weight_grad_parts(n))
+            for n in (frame_tiles, word_tiles))
+        key = (plan.ld_frames, plan.ld_words, parts)
+        found = self._workspace.get(key)
+        if found is None:
+            self._workspace.clear()
+            channels, layers = self.config.channels, self.config.layers
+            zeros = lambda *shape: torch.zeros(  # noqa: E731
+                shape, dtype=torch.float32, device=self.device)
+            slab = channels * 3 * self.config.num_features + channels
+            found = {
+                'frames': zeros(layers + 1, channels, plan.ld_frames),
+                'words': zeros(layers + 1, channels, plan.ld_words),
+                'frame_grad': zeros(2, channels, plan.ld_frames),
+                'word_grad': zeros(2, channels, plan.ld_words),
+                'logits': zeros(plan.ld_words),
+                'dlogit': zeros(plan.ld_words),
+                'slabs': zeros(max(parts, 1) * slab)}
+            self._workspace[key] = found
+        return found
+
+    def _forward(self, batch, training=False):
+        """The forward launches of a step; returns the step's buffers, whose
+        'logits' then hold the packed logits [ld_words].  `training`: with
+        the dropout masks of the step (never for validation)."""
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_f, ld_w = plan.ld_frames, plan.ld_words
+        frames, words = runtime.AXIS_FRAMES, runtime.AXIS_WORDS
+        buffers = self._buffers(plan)
+        stream = runtime.stream()
+        drop = training and self.dropout > 0.
+        word_tiles = meta[('tiles', words, WORD_TILE)]
+        table, bounds = meta['table'], meta['bounds']
+        word_segment = meta['word_segment']
+        mode = runtime.REDUCTIONS[config.downsample_method]
+        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
+
+        # ---- forward, every layer's output kept (model/core.py:91-107,138)
+        h, d = buffers['frames'], buffers['words']
+        self._encoder_forward(batch, h, drop)
+        runtime.check(lib.emph_segment_reduce(
+            h[layers].data_ptr(), ld_f, bounds.data_ptr(), d[0].data_ptr(),
+            ld_w, channels, table.data_ptr(), word_segment.data_ptr(), ld_w,
+            mode, stream), 'emph_segment_reduce')
+        for i, name in enumerate(decoder):
+            self._conv(self._forward_packs[name],
+                       self._parameter(f'{name}.bias'), d[i], d[i + 1], ld_w,
+                       channels, 'relu', word_tiles, WORD_TILE)
+            if drop:
+                self._dropout(name, d[i + 1])
+        logits = buffers['logits']
+        runtime.check(lib.emph_output_layer(
+            d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
+            self._parameter('output_layer.bias'), channels, 3,
+            table.data_ptr(), word_segment.data_ptr(), ld_w, words, 0,
+            logits.data_ptr(), None, stream), 'emph_output_layer')
+        return buffers
+
+    def _forward_backward(self, batch):
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_f, ld_w = plan.ld_frames, plan.ld_words
+        buffers = self._forward(batch, training=True)
+        stream = runtime.stream()
+        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
+        word_grad_tiles = meta[('tiles', runtime.AXIS_WORDS, GRAD_TILE)]
+        table, bounds = meta['table'], meta['bounds']
+        word_segment = meta['word_segment']
+        mode = runtime.REDUCTIONS[config.downsample_method]
+        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
+        d = buffers['words']
+        logits, dlogit = buffers['logits'], buffers['dlogit']
+
+        # ---- loss (train/core.py:315-353) and backward
+        runtime.check(lib.emph_loss_grad(
+            logits.data_ptr(), batch.targets.data_ptr(),
+            word_segment.data_ptr(), ld_w, plan.total_words,
+            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
+            dlogit.data_ptr(), stream), 'emph_loss_grad')
+        dd, dh = buffers['word_grad'], buffers['frame_grad']
+        runtime.check(lib.emph_output_layer_backward(
+            dlogit.data_ptr(), d[layers].data_ptr(), ld_w,
+            self._parameter('output_layer.weight'), word_segment.data_ptr(),
+            channels, 3, ld_w, self._gradient('output_layer.weight'),
+            self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
+            stream), 'emph_output_layer_backward')
+
+        dword = self._backward_stack(
+            batch, buffers, decoder, d, dd, ld_w, word_grad_tiles, word_tiles,
+            WORD_TILE)
+        runtime.check(lib.emph_segment_broadcast(
+            dword.data_ptr(), ld_w, bounds.data_ptr(), dh[0].data_ptr(), ld_f,
+            channels, table.data_ptr(), frame_tiles.data_ptr(),
+            frame_tiles.numel() // runtime.TILE_FIELDS, mode, stream),
+            'emph_segment_broadcast')
+        self._encoder_backward(batch, buffers)
+
+
+class EncoderTrainer(_Step):
+    """`Trainer` for the models without a word decoder, downsample_location
+    'inference' and 'loss' (`check_encoder_supported`); see the module
+    docstring.  The same interface: `data.Loader` and `train.evaluate` take
+    either.  `logits` is the model in eval mode for both locations
+    (`model/core.py:109-138`): encoder, reduce, word-rate output layer, no
+    dropout."""
+
+    _check = staticmethod(check_encoder_supported)
+
+    def _buffers(self, plan):
+        """The activations and gradients of a step for a packed layout, kept
+        between steps (zero at first, so that padding columns stay finite)."""
+        frame_tiles = len(plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
+        parts = int(self.lib.emph_conv_weight_grad_parts(frame_tiles))
+        head_parts = int(self.lib.emph_frame_head_parts(frame_tiles))
+        key = (plan.ld_frames, plan.ld_words, parts, head_parts, frame_tiles)
+        found = self._workspace.get(key)
+        if found is None:
+            self._workspace.clear()
+            channels, layers = self.config.channels, self.config.layers
+            zeros = lambda *shape, dtype=torch.float32: torch.zeros(  # noqa: E731
+                shape, dtype=dtype, device=self.device)
+            slab = channels * 3 * self.config.num_features + channels
+            found = {
+                'frames': zeros(layers + 1, channels, plan.ld_frames),
+                'words': zeros(1, channels, plan.ld_words),
+                'frame_grad': zeros(2, channels, plan.ld_frames),
+                'word_grad': zeros(1, channels, plan.ld_words),
+                'logits': zeros(plan.ld_words),
+                'dlogit': zeros(plan.ld_words),
+                'frame_logits': zeros(plan.ld_frames),
+                'frame_dlogit': zeros(plan.ld_frames),
+                'partials': zeros(max(frame_tiles, 1), dtype=torch.float64),
+                'slabs': zeros(max(
+                    max(parts, 1) * slab,
+                    max(head_parts, 1) * (3 * channels + 1)))}
+            self._workspace[key] = found
+        return found
+
+    def _forward(self, batch, training=False):
+        """The forward launches; returns the step's buffers.  In training at
+        'inference' (`model/core.py:117-122`) their 'frame_logits' hold the
+        packed frame logits [ld_frames]; everywhere else - 'loss', and both
+        locations in eval mode, `model/core.py:109-138` - their 'logits' hold
+        the packed word logits [ld_words].  `training`: with the dropout
+        masks of the step."""
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_f, ld_w = plan.ld_frames, plan.ld_words
+        buffers = self._buffers(plan)
+        stream = runtime.stream()
+        h = buffers['frames']
+        self._encoder_forward(batch, h, training and self.dropout > 0.)
+        if training and config.downsample_location == 'inference':
+            tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+            runtime.check(lib.emph_frame_head(
+                h[layers].data_ptr(), ld_f,
+                self._parameter('output_layer.weight'),
+                self._parameter('output_layer.bias'), channels, 3,
+                tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS,
+                buffers['frame_logits'].data_ptr(), stream), 'emph_frame_head')
+            return buffers
+        table, word_segment = meta['table'], meta['word_segment']
+        d = buffers['words']
+        runtime.check(lib.emph_segment_reduce(
+            h[layers].data_ptr(), ld_f, meta['bounds'].data_ptr(),
+            d[0].data_ptr(), ld_w, channels, table.data_ptr(),
+            word_segment.data_ptr(), ld_w,
+            runtime.REDUCTIONS[config.downsample_method], stream),
+            'emph_segment_reduce')
+        runtime.check(lib.emph_output_layer(
+            d[0].data_ptr(), ld_w, self._parameter('output_layer.weight'),
+            self._parameter('output_layer.bias'), channels, 3,
+            table.data_ptr(), word_segment.data_ptr(), ld_w,
+            runtime.AXIS_WORDS, 0, buffers['logits'].data_ptr(), None, stream),
+            'emph_output_layer')
+        return buffers
+
+    def _forward_backward(self, batch):
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_f, ld_w = plan.ld_frames, plan.ld_words
+        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        n_tiles = frame_tiles.numel() // runtime.TILE_FIELDS
+        table, bounds = meta['table'], meta['bounds']
+        word_segment = meta['word_segment']
+        if config.downsample_location == 'inference' and \
+                (len(plan.words) == 0 or int(min(plan.words)) < 1):
+            raise ValueError(
+                "downsample_location 'inference' interpolates the targets of "
+                'every utterance from its words: an utterance has none')
+        buffers = self._forward(batch, training=True)
+        stream = runtime.stream()
+        h, dh = buffers['frames'], buffers['frame_grad']
+        if config.downsample_location == 'inference':
+            # ---- loss on the frames (train/core.py:324-353) and the head
+            logits, dlogit = buffers['frame_logits'], buffers['frame_dlogit']
+            runtime.check(lib.emph_frame_loss_grad(
+                logits.data_ptr(), batch.targets.data_ptr(),
+                bounds.data_ptr(), ld_w, table.data_ptr(),
+                frame_tiles.data_ptr(), n_tiles, plan.total_frames,
+                runtime.BCE_FORMS[config.loss],
+                runtime.UPSAMPLE_METHODS[config.upsample_method],
+                buffers['partials'].data_ptr(), self.loss.data_ptr(),
+                dlogit.data_ptr(), stream), 'emph_frame_loss_grad')
+            runtime.check(lib.emph_frame_head_backward(
+                dlogit.data_ptr(), h[layers].data_ptr(), ld_f,
+                self._parameter('output_layer.weight'), channels, 3,
+                frame_tiles.data_ptr(), n_tiles, buffers['slabs'].data_ptr(),
+                self._gradient('output_layer.weight'),
+                self._gradient('output_layer.bias'), dh[0].data_ptr(), ld_f,
+                stream), 'emph_frame_head_backward')
+        else:
+            # ---- loss on the words (train/core.py:341-353), the head and
+            # the reduce
+            d, dd = buffers['words'], buffers['word_grad']
+            logits, dlogit = buffers['logits'], buffers['dlogit']
+            runtime.check(lib.emph_loss_grad(
+                logits.data_ptr(), batch.targets.data_ptr(),
+                word_segment.data_ptr(), ld_w, plan.total_words,
+                runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
+                dlogit.data_ptr(), stream), 'emph_loss_grad')
+            runtime.check(lib.emph_output_layer_backward(
+                dlogit.data_ptr(), d[0].data_ptr(), ld_w,
+                self._parameter('output_layer.weight'),
+                word_segment.data_ptr(), channels, 3, ld_w,
+                self._gradient('output_layer.weight'),
+                self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
+                stream), 'emph_output_layer_backward')
+            runtime.check(lib.emph_segment_reduce_backward(
+                dd[0].data_ptr(), ld_w, bounds.data_ptr(),
+                h[layers].data_ptr(), ld_f, d[0].data_ptr(), dh[0].data_ptr(),
+                ld_f, channels, table.data_ptr(), frame_tiles.data_ptr(),
+                n_tiles, runtime.REDUCTIONS[config.downsample_method], stream),
+                'emph_segment_reduce_backward')
+        self._encoder_backward(batch, buffers)
+
+
+def make_trainer(config=None, **arguments):
+    """The step that trains `config`: a `Trainer` where `check_supported`
+    passes, an `EncoderTrainer` at downsample_location 'inference' and 'loss'
+    where `check_encoder_supported` passes; otherwise the refusal that names
+    the offending field, before a GPU is needed."""
+    config = config or api.active_config()
+    if config.downsample_location in ('inference', 'loss'):
+        check_encoder_supported(config)
+        return EncoderTrainer(config, **arguments)
+    check_supported(config)
+    return Trainer(config, **arguments)

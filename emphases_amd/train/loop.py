@@ -1,5 +1,6 @@
 """The training loop of the convolution model (`emphases/train/core.py:13-307`):
-resume, train, validate, save - around `Trainer.step`, fed by the resident
+resume, train, validate, save - around `Trainer.step` (`EncoderTrainer.step`
+at downsample_location 'inference' and 'loss': `make_trainer`), fed by the resident
 loader of `emphases_amd.data`.
 
 Deviations from the reference, besides those of the step (`train/core.py`
@@ -106,7 +107,10 @@ def train(dataset, directory, gpu=None, *, partition_dir,
     Returns the final checkpoint's path."""
     from .. import data
     config = config or api.active_config()
-    core.check_supported(config)        # before any file is read
+    if config.downsample_location in ('inference', 'loss'):
+        core.check_encoder_supported(config)        # before any file is read
+    else:
+        core.check_supported(config)
     core.check_precision(precision)
     directory = os.fspath(directory)
     os.makedirs(directory, exist_ok=True)
@@ -126,11 +130,11 @@ def train(dataset, directory, gpu=None, *, partition_dir,
         score, best = float(state['score']), float(state['best'])
         # (the seed keys the dropout masks; the step count, which the
         # optimizer state restores, continues their stream)
-        trainer = core.Trainer(
+        trainer = core.make_trainer(
             config, checkpoint=state, gpu=gpu, seed=seed,
             precision=precision)
     else:
-        trainer = core.Trainer(
+        trainer = core.make_trainer(
             config, gpu=gpu, seed=seed, precision=precision)
     train_loader = loader('train', trainer, max_training_frames)
     # (the reference's validation sampler is `Sampler(dataset)`: the default

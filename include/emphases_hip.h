@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 39
+#define EMPH_ABI_VERSION 40
 
 /* Segment-table fields */
 enum {
@@ -1326,6 +1326,73 @@ int emph_segment_reduce_backward(const float* dword, int64_t ldw, const int32_t*
  * aligned, as emph_activation_backward. */
 int emph_activation_gradient(const float* source, float* gradient, int64_t count,
                              int32_t activation, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* Frame-rate head: DOWNSAMPLE_LOCATION 'inference' in train mode            */
+/* ------------------------------------------------------------------------ */
+
+/* Interpolation of emphases.upsample (UPSAMPLE_METHOD, config/defaults.py:213-215) */
+enum { EMPH_UPSAMPLE_LINEAR = 0, EMPH_UPSAMPLE_NEAREST = 1 };
+
+/* emphases.upsample (emphases/core.py:472-544): word -> frame resolution
+ * inside every segment.  `x` [channels][ldw] on the packed word axis,
+ * `bounds` [2][ldw] as emph_segment_reduce, `out` [channels][ldx] on the
+ * packed frame axis, `tiles` the 64-wide tile table of the frame axis.  With
+ * c_w = start_w + (end_w - start_w) / 2, f_t = t + 0.5 and
+ * i(t) = #{w : c_w <= f_t} - 1 over the W words of the segment:
+ *   W == 1   x_0 on every frame
+ *   NEAREST  x[clamp(i, 0, W - 1)]
+ *   LINEAR   j = clamp(i, 0, W - 2), x_j + (x_{j+1} - x_j) / (c_{j+1} - c_j) (f_t - c_j)
+ *            (extrapolated at both ends, not clamped; every channel on its
+ *            own line)
+ * The words of a segment must be sorted, disjoint and non-empty.  Every frame
+ * of a segment with a word is written; a segment without words is left. */
+int emph_upsample(const float* x, int64_t ldw, const int32_t* bounds, float* out,
+                  int64_t ldx, int32_t channels, const int64_t* seg, const int32_t* tiles,
+                  int32_t n_tiles, int32_t method, void* stream);
+
+/* output_layer at frame rate (emphases/model/core.py:122): Conv1d(channels, 1,
+ * 3, 'same') inside every segment of the 64-wide frame tile table,
+ *   logits[t] = bias + sum_c sum_j weight[c][j] h[c][t + j - 1]
+ * h zero outside its segment (selected: what lies between the segments, NaN
+ * included, reaches no result).  `logits` [ldh] is written inside the
+ * segments only.  kernel_size 3, channels 1..1024; anything else returns
+ * EMPH_ERANGE and launches nothing. */
+int emph_frame_head(const float* h, int64_t ldh, const float* weight, const float* bias,
+                    int32_t channels, int32_t kernel_size, const int32_t* tiles,
+                    int32_t n_tiles, float* logits, void* stream);
+
+/* loss(training=True) at DOWNSAMPLE_LOCATION 'inference'
+ * (emphases/train/core.py:324-353): the target of a frame is emph_upsample of
+ * the packed word targets `targets` [ldw] (one channel), formed on the fly
+ * and, for EMPH_UPSAMPLE_LINEAR only, clamped to [0, 1] (train/core.py:335-336).
+ * `valid_frames` = N, the frames of all segments; form as emph_loss_grad: the
+ * mean over the N frames, dlogit = d loss / d logit in float with a float
+ * 1 / N.  Two launches: a wave per tile writes dlogit inside the segments and
+ * one double partial sum into `workspace` [n_tiles]; one workgroup adds the
+ * partials in a fixed order and rounds the mean to float once into loss[0].
+ * Every segment needs a word. */
+int emph_frame_loss_grad(const float* logits, const float* targets, const int32_t* bounds,
+                         int64_t ldw, const int64_t* seg, const int32_t* tiles,
+                         int32_t n_tiles, int64_t valid_frames, int32_t form, int32_t method,
+                         double* workspace, float* loss, float* dlogit, void* stream);
+
+/* Backward of emph_frame_head (emphases/model/core.py:122 under autograd), in
+ * one pass over h and dlogit:
+ *   dx[c][t] = sum_j weight[c][j] dlogit[t - j + 1]
+ *   dweight[c][j] = sum_t dlogit[t] h[c][t + j - 1]     dbias[0] = sum_t dlogit[t]
+ * inside every segment, dlogit and h zero outside it (selected).  Every dx
+ * element inside a segment is written exactly once.  Two launches: workgroup
+ * p of emph_frame_head_parts(n_tiles) owns a fixed contiguous run of tiles and
+ * writes slab p of 3 channels + 1 floats into `workspace`; the second adds
+ * the slabs in a fixed order that depends on their number alone.  kernel_size
+ * 3, channels 1..80; anything else returns EMPH_ERANGE and launches nothing. */
+int32_t emph_frame_head_parts(int32_t n_tiles);
+int emph_frame_head_backward(const float* dlogit, const float* h, int64_t ldh,
+                             const float* weight, int32_t channels, int32_t kernel_size,
+                             const int32_t* tiles, int32_t n_tiles, float* workspace,
+                             float* dweight, float* dbias, float* dx, int64_t ld_dx,
+                             void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Measurement                                                               */

@@ -3,7 +3,9 @@
     python tools/train_bench.py [--laps 7] [--seconds 1.0] [--out profiles/train_step.json]
     python tools/train_bench.py --precision bf16x3 --parent <checkout of the parent commit>
     python tools/train_bench.py --dropout 0.1 --parent <checkout of the parent commit>
+    python tools/train_bench.py --downsample_location inference loss --laps 3 --parent <checkout of the parent commit> --out profiles/train_step_locations.json
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --steps 20
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --downsample_location inference --steps 20
 
 The batch is what the reference's sampler fills up to (`MAX_TRAINING_FRAMES =
 75 000`, `config/defaults.py`): 75 utterances x 1 000 frames x 30 words,
@@ -29,6 +31,15 @@ With `--dropout P` one more contender, `ours_dropout`, is the same trainer
 under `Config(dropout=P)` (Philox masks, `emph_dropout`), and both torch
 models gain `torch.nn.Dropout(P)` after each activation, as the reference
 builds them under DROPOUT; `ours` stays the step without dropout.
+
+With `--downsample_location inference` and / or `loss` the contenders are the
+decoder-less models instead: `ours_<location>` is
+`emphases_amd.train.EncoderTrainer.step` there, `torch_fp32_<location>` the
+same model (input layer, frame encoder, output layer; the word sums as the
+batched matmul at 'loss', the frame targets of `emphases_amd.upsample`, made
+once outside the timed region and clamped, at 'inference') with autograd and
+`torch.optim.Adam` in float32, and `ours_parent` (with `--parent`) the
+'intermediate' step of the parent checkout on the same batch.
 
 Every utterance has the same lengths, so the padded batch of the torch model
 and the ragged batch of this package compute the same function.  A lap of one
@@ -101,6 +112,30 @@ class TorchModel(torch.nn.Module):
         return self.output_layer(self.word_decoder(words))
 
 
+class TorchEncoderModel(torch.nn.Module):
+    """`emphases.Model` without a word decoder (`model/core.py:28-30`) in
+    train mode: frame logits at 'inference', word logits at 'loss'."""
+
+    def __init__(self, state, location):
+        super().__init__()
+        conv = lambda c_in, c_out: torch.nn.Conv1d(  # noqa: E731
+            c_in, c_out, kernel_size=3, padding='same')
+        self.location = location
+        self.input_layer = conv(80, 80)
+        self.frame_encoder = torch.nn.Sequential(*[
+            module for _ in range(6)
+            for module in [conv(80, 80), torch.nn.ReLU()]])
+        self.output_layer = conv(80, 1)
+        self.load_state_dict(
+            {name: torch.from_numpy(value) for name, value in state.items()})
+
+    def forward(self, features, membership):
+        frames = self.frame_encoder(self.input_layer(features))
+        if self.location == 'loss':
+            frames = torch.bmm(frames, membership.to(frames.dtype))
+        return self.output_layer(frames)
+
+
 def torch_step(model, optimizer, scaler, features, membership, targets):
     with torch.autocast('cuda', enabled=scaler is not None):
         loss = torch.nn.functional.binary_cross_entropy_with_logits(
@@ -168,6 +203,36 @@ def run_lap(function, steps):
     return timed(function, steps)
 
 
+def locations(arguments, batch):
+    """The contenders of `--downsample_location`."""
+    contenders, keep = {}, []
+    for location in arguments.downsample_location:
+        config = emphases_amd.Config(downsample_location=location)
+        state = train.initial_state(config, seed=0)
+        ours = train.EncoderTrainer(config, checkpoint=state, gpu=0)
+        prepared = ours.prepare(*batch)
+        keep.append((ours, prepared))
+        contenders[f'ours_{location}'] = \
+            lambda o=ours, p=prepared: o.step(p)
+        if arguments.no_torch or arguments.only:
+            continue
+        features, frame_lengths, bounds, word_lengths, targets = batch
+        if location == 'inference':
+            targets = torch.clamp(emphases_amd.upsample(
+                targets.cuda(), bounds, word_lengths, frame_lengths, config),
+                0., 1.)
+        features, bounds, targets = features.cuda(), bounds.cuda(), targets.cuda()
+        frame = torch.arange(FRAMES, device='cuda')[None, :, None]
+        membership = ((frame >= bounds[:, 0, None, :]) &
+                      (frame < bounds[:, 1, None, :])).float()
+        model = TorchEncoderModel(state, location).cuda()
+        optimizer = torch.optim.Adam(model.parameters())
+        contenders[f'torch_fp32_{location}'] = (
+            lambda m=model, o=optimizer, f=features, b=membership, t=targets:
+            torch_step(m, o, None, f, b, t))
+    return contenders
+
+
 def serve():
     """The child of `Parent`: 0 -> one step, its loss; n -> a timed lap."""
     torch.cuda.set_device(0)
@@ -180,6 +245,51 @@ def serve():
             print(float(ours.step(prepared)), flush=True)
         else:
             print(timed(lambda: ours.step(prepared), steps), flush=True)
+
+
+def compare(arguments, contenders):
+    """Alternating laps of the `--downsample_location` contenders."""
+    parent = None
+    if arguments.only is None and arguments.parent:
+        parent = contenders['ours_parent'] = Parent(arguments.parent)
+    try:
+        first = {}
+        for name, function in contenders.items():
+            first[name] = float(function())
+            for _ in range(4):
+                function()
+        torch.cuda.synchronize()
+        steps = {}
+        for name, function in contenders.items():
+            probe = run_lap(function, 5)
+            steps[name] = arguments.steps or max(
+                5, int(arguments.seconds * 1e3 / probe))
+        if arguments.only:
+            name = f'ours_{arguments.downsample_location[0]}'
+            timed(contenders[name], steps[name])
+            print(json.dumps({f'{name}_steps': steps[name]}))
+            return
+        laps = {name: [] for name in contenders}
+        for _ in range(arguments.laps):
+            for name, function in contenders.items():
+                laps[name].append(run_lap(function, steps[name]))
+    finally:
+        if parent is not None:
+            parent.close()
+    record = {
+        'batch': {'utterances': ITEMS, 'frames': FRAMES, 'words': WORDS},
+        'device': torch.cuda.get_device_name(0),
+        'laps': arguments.laps, 'steps_per_lap': steps, 'first_loss': first,
+        'ms_per_step': {
+            name: {'median': float(np.median(values)),
+                   'min': float(np.min(values)), 'max': float(np.max(values))}
+            for name, values in laps.items()},
+        'ms_per_step_laps': laps}
+    print(json.dumps(record))
+    if arguments.out:
+        with open(arguments.out, 'w') as file:
+            json.dump(record, file, indent=1)
+            file.write('\n')
 
 
 def main():
@@ -195,6 +305,9 @@ def main():
         choices=getattr(train, 'PRECISIONS', ('f32',)))
     parser.add_argument('--parent', default=None)
     parser.add_argument('--dropout', type=float, default=None)
+    parser.add_argument(
+        '--downsample_location', nargs='+', default=None,
+        choices=('inference', 'loss'))
     parser.add_argument('--no-torch', action='store_true')
     parser.add_argument('--serve', action='store_true', help=argparse.SUPPRESS)
     arguments = parser.parse_args()
@@ -202,6 +315,8 @@ def main():
         return serve()
     torch.cuda.set_device(0)
     batch = make_batch()
+    if arguments.downsample_location:
+        return compare(arguments, locations(arguments, batch))
     state = train.initial_state(emphases_amd.DEFAULT, seed=0)
     dropped = None if arguments.dropout is None else \
         emphases_amd.Config(dropout=arguments.dropout)
