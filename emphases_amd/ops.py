@@ -27,11 +27,14 @@ Autograd.  `conv1d_same_act` (gradients of `x`, `weight`, `bias`) and
 `segment_reduce` (gradient of `x`) are differentiable once
 (`torch.library.register_autograd`; a backward under `create_graph=True`,
 the way to a second backward, raises) and carry a
-`register_fake` shape rule; `logmel`, `encoder_layer` and `prominence_forward`
-stay non-differentiable.  The backward runs on the library's kernels
+`register_fake` shape rule; so is `encoder_layer` (gradients of `x` and of
+all twelve parameters; 80 channels in 2 heads, its dropouts the identity:
+see its docstring); `logmel` and `prominence_forward` stay
+non-differentiable.  The backward runs on the library's kernels
 (`emph_activation_gradient`, `emph_conv_weight_grad_any`, `emph_conv1d` on the
-flipped pack, `emph_segment_reduce_backward`), without atomics: the same
-inputs give the same bits.
+flipped pack, `emph_segment_reduce_backward`, `emph_attention_backward`,
+`emph_add_layernorm_backward`), without atomics: the same inputs give the
+same bits.
 
 Two paths of `conv1d_same_act`.  A weight that has never changed since the op
 first saw it (inference) takes the kernels it always took, its packs made
@@ -40,6 +43,15 @@ updates it in place) is packed ON THE DEVICE (`emph_take` through an index
 table made once per weight shape, no device-to-host copy) and runs as
 direct-form `emph_conv1d` on 64-position tiles, as `train.Trainer` does.  The
 two paths differ at float32 rounding (Winograd against direct form).
+
+Two paths of `encoder_layer`, in the same way.  A parameter set of which no
+tensor has changed since the op first saw it runs on the layer's fused
+inference engine (packs made once on the host; the bits it always gave,
+whether or not anything requires grad).  Once a tensor's version has changed,
+the layer runs as the unfused sequence of launches that its backward also
+recomputes, on weights packed on the device: no `Engine` is rebuilt and
+nothing is copied to the host per step.  The two paths differ at float32
+rounding (fused chain against separate launches).
 
 One plan per batch: the packed layout of a set of `cu_*` (and `bounds`)
 values, its device metadata and its device column indices are kept in a small
@@ -308,21 +320,27 @@ class _ByStorage:
         return value
 
 
-_device_packs = _ByStorage(64)
+_device_packs = _ByStorage(256)
 _first_versions = _ByStorage(256)
 
 
-def _device_pack(weight, index, flipped):
+def _device_pack(weight, index, flipped, rows=None):
     """The direct-form MFMA pack of `weight` (or of its flipped transpose),
-    built on the device by one `emph_take`; kept per (storage, version)."""
-    key = _ByStorage.key(weight, weight._version, flipped)
+    built on the device by one `emph_take`; kept per (storage, version).
+    `rows` = (first, last): of those rows of a 2-D `weight` alone, as a
+    kernel_size-1 convolution (the Linear layers of `encoder_layer`; None for
+    a 2-D weight: all of its rows)."""
+    key = _ByStorage.key(weight, weight._version, flipped, rows)
     found = _device_packs.get(weight, key)
     if found is not None:
         return found
-    table = _device_tables(tuple(weight.shape), index)[1 if flipped else 0]
     source = weight.detach()
     if source.dtype != torch.float32 or not source.is_contiguous():
         source = source.to(torch.float32).contiguous()
+    if source.dim() == 2:
+        first, last = rows or (0, source.shape[0])
+        source = source[first:last].unsqueeze(2)
+    table = _device_tables(tuple(source.shape), index)[1 if flipped else 0]
     pack = torch.empty(table.numel(), dtype=torch.float32, device=weight.device)
     runtime.check(runtime.library().emph_take(
         source.data_ptr(), table.data_ptr(), pack.data_ptr(), pack.numel(),
@@ -638,6 +656,195 @@ def _layer_engine(key, index, channels, heads, tensors):
     return engine_module.Engine(config, state, index)
 
 
+LAYER_CHANNELS, LAYER_HEADS = 80, 2      # emph_attention_backward
+LAYER_EPS = cfg.Config(architecture='transformer').layer_norm_eps
+
+
+class _LayerRun:
+    """One encoder layer as an UNFUSED sequence of launches on the packed
+    layout that keeps every intermediate (what the backward walks back
+    through, and the forward of a parameter set that is being trained): Q / K
+    and V by `emph_conv1d` k = 1, `emph_attention`, out_proj,
+    `emph_add_layernorm`, linear1 + ReLU, linear2, `emph_add_layernorm`.  The
+    weights are packed on the device (`_device_pack`): nothing is copied to
+    the host."""
+
+    def __init__(self, x, tensors, heads, layout, index):
+        (self.in_w, self.in_b, self.out_w, self.out_b, self.norm1_w,
+         self.norm1_b, self.ff1_w, self.ff1_b, self.ff2_w, self.ff2_b,
+         self.norm2_w, self.norm2_b) = tensors
+        self.layout, self.index, self.heads = layout, index, int(heads)
+        self.ld = ld = layout.plan.ld_frames
+        self.channels = channels = int(x.shape[0])
+        self.device = x.device
+        self.lib = runtime.library()
+        self.keep = []
+        self.tiles, self.n_tiles = layout.tiles(DIRECT_TILE)
+        bias = _float_pointer(self.in_b, self.keep)
+        self.x = layout.scatter(x, layout.frame_columns, ld)
+        self.qk = self.zeros(2 * channels)
+        self.conv(self.x, self.qk, self.pack(self.in_w, (0, 2 * channels)),
+                  bias, channels, 2 * channels)
+        self.v = torch.zeros((ld, channels), dtype=torch.float32,
+                             device=self.device)
+        self.conv(self.x, self.v,
+                  self.pack(self.in_w, (2 * channels, 3 * channels)),
+                  bias + 4 * 2 * channels, channels, channels, transpose=True)
+        self.attended = self.zeros(channels)
+        runtime.check(self.lib.emph_attention(
+            self.qk.data_ptr(), self.v.data_ptr(), self.attended.data_ptr(),
+            ld, channels, self.heads, self.tiles.data_ptr(), self.n_tiles,
+            DIRECT_TILE, None, runtime.stream()), 'emph_attention')
+        self.projected = self.zeros(channels)
+        self.conv(self.attended, self.projected, self.pack(self.out_w),
+                  _float_pointer(self.out_b, self.keep), channels, channels)
+        self.normed1 = self.zeros(channels)
+        self.add_layernorm(self.x, self.projected, self.normed1, self.norm1_w,
+                           self.norm1_b)
+        hidden = int(self.ff1_w.shape[0])
+        self.hidden = self.zeros(hidden)
+        self.conv(self.normed1, self.hidden, self.pack(self.ff1_w),
+                  _float_pointer(self.ff1_b, self.keep), channels, hidden,
+                  activation='relu')
+        self.fed = self.zeros(channels)
+        self.conv(self.hidden, self.fed, self.pack(self.ff2_w),
+                  _float_pointer(self.ff2_b, self.keep), hidden, channels)
+        self.normed2 = self.zeros(channels)
+        self.add_layernorm(self.normed1, self.fed, self.normed2, self.norm2_w,
+                           self.norm2_b)
+
+    def zeros(self, rows):
+        return torch.zeros((rows, self.ld), dtype=torch.float32,
+                           device=self.device)
+
+    def pack(self, weight, rows=None, flipped=False):
+        return _device_pack(weight, self.index, flipped, rows)
+
+    def conv(self, x, y, pack, bias, c_in, c_out, activation=None,
+             transpose=False):
+        runtime.check(self.lib.emph_conv1d(
+            x.data_ptr(), self.ld, y.data_ptr(),
+            c_out if transpose else self.ld, pack.data_ptr(), bias, c_in,
+            c_out, 1, runtime.ACTIVATIONS[activation], self.tiles.data_ptr(),
+            self.n_tiles, DIRECT_TILE, int(transpose), runtime.stream()),
+            'emph_conv1d')
+
+    def add_layernorm(self, x, r, y, gamma, beta):
+        runtime.check(self.lib.emph_add_layernorm(
+            x.data_ptr(), r.data_ptr(), y.data_ptr(), self.ld, self.channels,
+            _float_pointer(gamma, self.keep), _float_pointer(beta, self.keep),
+            LAYER_EPS, 0, self.ld, runtime.stream()), 'emph_add_layernorm')
+
+    # ---- the way back
+
+    def layernorm_backward(self, summed, gamma, dy):
+        """(ds, dgamma, dbeta) of `emph_add_layernorm_backward`."""
+        ds = self.zeros(self.channels)
+        dgamma = torch.empty(self.channels, dtype=torch.float32,
+                             device=self.device)
+        dbeta = torch.empty_like(dgamma)
+        parts = int(self.lib.emph_add_layernorm_backward_parts(self.n_tiles))
+        workspace = torch.empty(max(1, parts * 2 * self.channels),
+                                dtype=torch.float32, device=self.device)
+        runtime.check(self.lib.emph_add_layernorm_backward(
+            summed.data_ptr(), _float_pointer(gamma, self.keep), dy.data_ptr(),
+            ds.data_ptr(), self.ld, self.channels, LAYER_EPS,
+            self.tiles.data_ptr(), self.n_tiles, GRAD_TILE,
+            workspace.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+            runtime.stream()), 'emph_add_layernorm_backward')
+        return ds, dgamma, dbeta
+
+    def weight_grad(self, dy, x, c_in, c_out, dweight, dbias):
+        """dweight [c_out, c_in] and dbias [c_out] (views to fill) of a Linear
+        layer: `emph_conv_weight_grad_any` with kernel_size 1."""
+        if not self.n_tiles:
+            dweight.zero_()
+            dbias.zero_()
+            return
+        workspace = torch.empty(
+            int(self.lib.emph_conv_weight_grad_any_workspace(
+                c_in, c_out, 1, self.n_tiles)),
+            dtype=torch.float32, device=self.device)
+        runtime.check(self.lib.emph_conv_weight_grad_any(
+            dy.data_ptr(), self.ld, x.data_ptr(), self.ld, c_in, c_out, 1,
+            self.tiles.data_ptr(), self.n_tiles, GRAD_TILE,
+            workspace.data_ptr(), dweight.data_ptr(), dbias.data_ptr(),
+            runtime.stream()), 'emph_conv_weight_grad_any')
+
+    def backward(self, grad, need):
+        """The thirteen gradients (packed dx gathered by the caller; None
+        where `need` is False), walking back only as far as `need` asks."""
+        channels, ld, device = self.channels, self.ld, self.device
+        hidden = self.hidden.shape[0]
+        out = [None] * 13
+
+        def linear_grads(dy, x, weight, slot, rows=None):
+            if not (need[slot] or need[slot + 1]):
+                return
+            c_out, c_in = weight.shape
+            dweight = torch.empty((c_out, c_in), dtype=torch.float32,
+                                  device=device)
+            dbias = torch.empty(c_out, dtype=torch.float32, device=device)
+            for first in range(0, c_out, rows or c_out):
+                last = first + (rows or c_out)
+                self.weight_grad(dy[first:last], x, c_in, last - first,
+                                 dweight[first:last], dbias[first:last])
+            out[slot] = dweight if need[slot] else None
+            out[slot + 1] = dbias if need[slot + 1] else None
+
+        dy = self.layout.scatter(grad, self.layout.frame_columns, ld)
+        ds2, dgamma, dbeta = self.layernorm_backward(
+            self.normed1 + self.fed, self.norm2_w, dy)
+        out[11], out[12] = (dgamma if need[11] else None,
+                            dbeta if need[12] else None)
+        if not any(need[:11]):
+            return out
+        linear_grads(ds2, self.hidden, self.ff2_w, 9)
+        if not any(need[:9]):
+            return out
+        dhidden = self.zeros(hidden)
+        self.conv(ds2, dhidden, self.pack(self.ff2_w, flipped=True), None,
+                  channels, hidden)
+        runtime.check(self.lib.emph_activation_gradient(
+            self.hidden.data_ptr(), dhidden.data_ptr(), dhidden.numel(),
+            runtime.ACTIVATIONS['relu'], runtime.stream()),
+            'emph_activation_gradient')
+        linear_grads(dhidden, self.normed1, self.ff1_w, 7)
+        if not any(need[:7]):
+            return out
+        dnormed1 = self.zeros(channels)
+        self.conv(dhidden, dnormed1, self.pack(self.ff1_w, flipped=True), None,
+                  hidden, channels)
+        dnormed1 += ds2
+        ds1, dgamma, dbeta = self.layernorm_backward(
+            self.x + self.projected, self.norm1_w, dnormed1)
+        out[5], out[6] = (dgamma if need[5] else None,
+                          dbeta if need[6] else None)
+        linear_grads(ds1, self.attended, self.out_w, 3)
+        if not any(need[:3]):
+            return out
+        dattended = self.zeros(channels)
+        self.conv(ds1, dattended, self.pack(self.out_w, flipped=True), None,
+                  channels, channels)
+        dqkv = self.zeros(3 * channels)
+        workspace = torch.empty(
+            max(1, int(self.lib.emph_attention_backward_workspace(
+                ld, self.heads))), dtype=torch.float32, device=device)
+        runtime.check(self.lib.emph_attention_backward(
+            self.qk.data_ptr(), self.v.data_ptr(), self.attended.data_ptr(),
+            dattended.data_ptr(), dqkv.data_ptr(), ld, channels, self.heads,
+            self.tiles.data_ptr(), self.n_tiles, GRAD_TILE,
+            workspace.data_ptr(), runtime.stream()), 'emph_attention_backward')
+        linear_grads(dqkv, self.x, self.in_w, 1, rows=channels)
+        if need[0]:
+            dx = self.zeros(channels)
+            self.conv(dqkv, dx, self.pack(self.in_w, flipped=True), None,
+                      3 * channels, channels)
+            dx += ds1
+            out[0] = dx
+        return out
+
+
 @torch.library.custom_op('emphases_amd::encoder_layer', mutates_args=())
 def encoder_layer(x: torch.Tensor, in_proj_weight: torch.Tensor,
                   in_proj_bias: torch.Tensor, out_proj_weight: torch.Tensor,
@@ -647,15 +854,44 @@ def encoder_layer(x: torch.Tensor, in_proj_weight: torch.Tensor,
                   linear2_bias: torch.Tensor, norm2_weight: torch.Tensor,
                   norm2_bias: torch.Tensor, cu_T: torch.Tensor,
                   heads: int) -> torch.Tensor:
-    """One `nn.TransformerEncoderLayer` (post-LN, ReLU, eps 1e-5; dropout is the
-    identity at inference) as `transformer.py:18-30` stacks them, over N
-    segments back to back (attention within a segment only): x `[C, sum T_i]`
-    -> `[C, sum T_i]`; no positional encoding is added."""
+    """One `nn.TransformerEncoderLayer` (post-LN, ReLU, eps 1e-5) as
+    `transformer.py:18-30` stacks them, over N segments back to back
+    (attention within a segment only): x `[C, sum T_i]` -> `[C, sum T_i]`; no
+    positional encoding is added.
+
+    DROPOUT IS THE IDENTITY, in the forward and in the backward: the
+    reference's layer TRAINS with its internal dropout of 0.1 (attention
+    weights, both residual branches, the feed-forward), which this op does not
+    draw - a deliberate deviation (dropout inside the attention kernel is not
+    built).
+
+    A parameter set that has never changed since the op first saw it runs on
+    the fused inference engine of the layer (its packs made once on the host);
+    one whose version has changed (an optimizer updates it in place) runs the
+    unfused, device-packed sequence of `_LayerRun` - see the module docstring.
+
+    Backward (once): the context saves the inputs only; the layer is
+    recomputed by `_LayerRun`, which keeps every intermediate, and walked back
+    through `emph_add_layernorm_backward`, `emph_attention_backward`,
+    `emph_activation_gradient`, `emph_conv_weight_grad_any` (kernel_size 1;
+    in_proj as three row slices of dQ | dK | dV) and `emph_conv1d` on the
+    flipped device packs (in_proj: one launch, c_in 240).  Only the gradients
+    `needs_input_grad` asks for are computed, and the walk stops where nothing
+    upstream needs it.  Channels other than 80 or heads other than 2 raise
+    NotImplementedError in the backward (the forward accepts what
+    `emph_attention` does)."""
     index = _device_index(x)
     counts, _ = _counts(cu_T)
     tensors = (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias,
                norm1_weight, norm1_bias, linear1_weight, linear1_bias,
                linear2_weight, linear2_bias, norm2_weight, norm2_bias)
+    if any([_weight_changes(tensor) for tensor in tensors]):
+        if int(counts.sum()) != x.shape[1]:
+            raise ValueError('cu_T does not cover the columns of x')
+        layout = _layout(x.device, counts)
+        with torch.cuda.device(index):
+            run = _LayerRun(x, tensors, heads, layout, index)
+            return run.normed2.index_select(1, layout.frame_columns)
     key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in tensors)
     engine = _layer_engine(key, index, int(x.shape[0]), int(heads),
                            _Borrowed(tensors))
@@ -669,6 +905,50 @@ def encoder_layer(x: torch.Tensor, in_proj_weight: torch.Tensor,
             engine.frame_encoder, packed, other, plan.ld_frames, plan, meta,
             runtime.AXIS_FRAMES, meta['tile'], 'op', positioned=True)
         return _gather(encoded, plan.frame_off, plan.frames)
+
+
+@encoder_layer.register_fake
+def _encoder_layer_fake(x, in_proj_weight, in_proj_bias, out_proj_weight,
+                        out_proj_bias, norm1_weight, norm1_bias, linear1_weight,
+                        linear1_bias, linear2_weight, linear2_bias,
+                        norm2_weight, norm2_bias, cu_T, heads):
+    return x.new_empty(x.shape, dtype=torch.float32)
+
+
+def _layer_setup(ctx, inputs, output):
+    ctx.heads = inputs[14]
+    ctx.save_for_backward(*inputs[:14])
+
+
+def _layer_backward(ctx, grad):
+    _once('encoder_layer')
+    saved = ctx.saved_tensors
+    x, tensors, cu_T = saved[0], saved[1:13], saved[13]
+    need = list(ctx.needs_input_grad[:13])
+    if x.shape[0] != LAYER_CHANNELS:
+        raise NotImplementedError(
+            f'the backward of encoder_layer supports x of {LAYER_CHANNELS} '
+            f'channels only, not {x.shape[0]}')
+    if ctx.heads != LAYER_HEADS:
+        raise NotImplementedError(
+            f'the backward of encoder_layer supports heads={LAYER_HEADS} '
+            f'only, not heads={ctx.heads}')
+    if not any(need):
+        return (None,) * 15
+    index = _device_index(grad)
+    counts, _ = _counts(cu_T)
+    layout = _layout(x.device, counts)
+    with torch.cuda.device(index):
+        run = _LayerRun(x.detach(), tensors, ctx.heads, layout, index)
+        grads = run.backward(grad, need)
+        if grads[0] is not None:
+            grads[0] = grads[0].index_select(1, layout.frame_columns)
+    grads = [None if g is None else g.to(source.dtype).reshape(source.shape)
+             for g, source in zip(grads, saved[:13])]
+    return (*grads, None, None)
+
+
+encoder_layer.register_autograd(_layer_backward, setup_context=_layer_setup)
 
 
 @torch.library.custom_op('emphases_amd::prominence_forward', mutates_args=())

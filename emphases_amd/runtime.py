@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -242,6 +242,14 @@ SIGNATURES = {
     'emph_frame_head_backward': (_c.c_int, [
         _ptr, _ptr, _i64, _ptr, _i32, _i32, _ptr, _i32, _ptr, _ptr, _ptr,
         _ptr, _i64, _ptr]),
+    'emph_attention_backward_workspace': (_i64, [_i64, _i32]),
+    'emph_attention_backward': (_c.c_int, [
+        _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i32, _i32, _ptr, _i32, _i32, _ptr,
+        _ptr]),
+    'emph_add_layernorm_backward_parts': (_i32, [_i32]),
+    'emph_add_layernorm_backward': (_c.c_int, [
+        _ptr, _ptr, _ptr, _ptr, _i64, _i32, _f32, _ptr, _i32, _i32, _ptr, _ptr,
+        _ptr, _ptr]),
     'emph_adam_step': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _i64, _c.c_double, _c.c_double, _f32, _f32,
         _f32, _ptr]),

@@ -4,7 +4,8 @@ forward with every layer kept, masked loss, backward and Adam
 validate, save (`train/core.py:13-307`) - fed by `emphases_amd.data`; and
 `TorchModel`, the same architecture as a `torch.nn.Module` on the
 differentiable operator seams for the configurations the fused steps refuse.
-`EncoderTrainer` is the step of the models without a word decoder
+`TransformerModel` is the Transformer architecture on the same seams (the
+fused steps, `make_trainer` and `train` refuse it).  `EncoderTrainer` is the step of the models without a word decoder
 (downsample_location 'inference' and 'loss'); `make_trainer` picks the class."""
 from .core import (  # noqa: F401
     PRECISIONS, Batch, EncoderTrainer, Trainer, adam_state_dict, check_batch,
@@ -14,4 +15,6 @@ from .core import (  # noqa: F401
 from . import dropout  # noqa: F401
 from .model import (  # noqa: F401
     TorchModel, check_model_supported, initial_model_state, loss_fn)
+from .transformer_model import (  # noqa: F401
+    TransformerModel, check_transformer_supported, initial_transformer_state)
 from .loop import evaluate, latest_path, train  # noqa: F401

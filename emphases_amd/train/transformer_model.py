@@ -1,0 +1,224 @@
+"""The reference's `emphases.Model` under ARCHITECTURE = 'transformer'
+(`emphases/model/core.py:11-138`, `model/layers/transformer.py:13-52`) as a
+`torch.nn.Module` on the differentiable operator seams: `conv1d_same_act` for
+the input and output layers, `encoder_layer` once per layer of a stack,
+`segment_reduce` between the frames and the words.  At downsample_location
+'intermediate' the word decoder is a second Transformer over the words; at
+'loss' there is none.
+
+Every utterance runs alone, as inference runs it: attention stays within an
+utterance, and the sinusoidal table (`weights.positional_encoding`) is
+gathered by the position inside the utterance.
+
+Deliberate deviation: dropout is the identity.  The reference's
+`TransformerEncoderLayer` trains with its internal dropout of 0.1 (attention
+weights, both residual branches, the feed-forward) and its
+`PositionalEncoding` with another 0.1; neither is drawn here (dropout inside
+the attention kernel is not built), so `train()` and `eval()` compute the
+same function.  `Config.dropout` (the conv stacks' switch) is refused.
+"""
+import collections
+import functools
+
+import numpy as np
+import torch
+
+from .. import config as cfg
+from .. import core as api
+from .. import ops  # noqa: F401  (registers torch.ops.emphases_amd)
+from .. import weights as weights_module
+
+CHANNELS, HEADS = 80, 2     # the backward of encoder_layer
+
+
+def check_transformer_supported(config):
+    """NotImplementedError, naming the field, for a configuration
+    `TransformerModel` does not cover."""
+    def refuse(field, supported):
+        raise NotImplementedError(
+            f'TransformerModel supports {field} {supported} only, not '
+            f'{field}={getattr(config, field)!r}')
+    if config.method != 'neural':
+        refuse('method', "'neural'")
+    if config.architecture != 'transformer':
+        refuse('architecture', "'transformer'")
+    if config.downsample_location not in ('intermediate', 'loss'):
+        # 'inference' needs `upsample` of the targets; 'input' the key-padding
+        # mask over zero-padded word pieces (emph_attention's key_counts),
+        # which emph_attention_backward does not take
+        refuse('downsample_location', "'intermediate' or 'loss'")
+    if config.channels != CHANNELS:
+        refuse('channels', str(CHANNELS))
+    if config.heads != HEADS:
+        refuse('heads', str(HEADS))
+    if config.dropout is not None:
+        refuse('dropout', 'None')
+    if config.loss not in ('bce', 'mse'):
+        refuse('loss', "'bce' or 'mse'")
+    if not config.mel_feature:
+        refuse('mel_feature', 'True (80..83 input features)')
+
+
+_LAYER_ORDER = ('self_attn.in_proj_weight', 'self_attn.in_proj_bias',
+                'self_attn.out_proj.weight', 'self_attn.out_proj.bias',
+                'linear1.weight', 'linear1.bias', 'linear2.weight',
+                'linear2.bias', 'norm1.weight', 'norm1.bias', 'norm2.weight',
+                'norm2.bias')
+
+
+def initial_transformer_state(config, seed=0):
+    """Bitwise the parameters of the reference's `emphases.Model()` after
+    `torch.manual_seed(seed)`: the torch modules built on the CPU in the
+    reference's construction order (`model/core.py:13-37`; a stack is ONE
+    `TransformerEncoderLayer` cloned `layers` times, so its layers start
+    equal; `PositionalEncoding` draws nothing).  The caller's generator is
+    left as it was."""
+    check_transformer_supported(config)
+    state = collections.OrderedDict()
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+
+        def conv(name, c_in, c_out, kernel_size):
+            module = torch.nn.Conv1d(
+                c_in, c_out, kernel_size=kernel_size, padding='same')
+            state[f'{name}.weight'] = module.weight.detach().numpy().copy()
+            state[f'{name}.bias'] = module.bias.detach().numpy().copy()
+
+        def stack(prefix):
+            module = torch.nn.TransformerEncoder(
+                torch.nn.TransformerEncoderLayer(
+                    config.channels, HEADS, dim_feedforward=config.channels),
+                config.layers, enable_nested_tensor=False)
+            values = dict(module.named_parameters())
+            for i in range(config.layers):
+                for name in _LAYER_ORDER:
+                    state[f'{prefix}.model.layers.{i}.{name}'] = \
+                        values[f'layers.{i}.{name}'].detach().numpy().copy()
+        conv('input_layer', config.num_features, config.channels,
+             config.encoder_kernel_size)
+        stack('frame_encoder')
+        if config.has_decoder:
+            stack('word_decoder')
+        conv('output_layer', config.channels, 1, config.decoder_kernel_size)
+    assert list(state) == list(weights_module.parameter_shapes(config))
+    return state
+
+
+class _Parameters(torch.nn.Module):
+    """A module that holds `name -> Parameter` (and sub-modules) in order."""
+
+    def __init__(self, **tensors):
+        super().__init__()
+        for name, value in tensors.items():
+            setattr(self, name, torch.nn.Parameter(
+                torch.from_numpy(np.array(value, dtype=np.float32))))
+
+
+class _Layer(torch.nn.Module):
+    """The parameters of one `nn.TransformerEncoderLayer`, under its names and
+    in the order of `weights.parameter_shapes`."""
+
+    def __init__(self, state, prefix):
+        super().__init__()
+        self.self_attn = _Parameters(
+            in_proj_weight=state[prefix + 'self_attn.in_proj_weight'],
+            in_proj_bias=state[prefix + 'self_attn.in_proj_bias'])
+        self.self_attn.out_proj = _Parameters(
+            weight=state[prefix + 'self_attn.out_proj.weight'],
+            bias=state[prefix + 'self_attn.out_proj.bias'])
+        for name in ('linear1', 'linear2', 'norm1', 'norm2'):
+            setattr(self, name, _Parameters(
+                weight=state[f'{prefix}{name}.weight'],
+                bias=state[f'{prefix}{name}.bias']))
+
+    def forward(self, x, cu):
+        attention = self.self_attn
+        return torch.ops.emphases_amd.encoder_layer(
+            x, attention.in_proj_weight, attention.in_proj_bias,
+            attention.out_proj.weight, attention.out_proj.bias,
+            self.norm1.weight, self.norm1.bias, self.linear1.weight,
+            self.linear1.bias, self.linear2.weight, self.linear2.bias,
+            self.norm2.weight, self.norm2.bias, cu, HEADS)
+
+
+@functools.lru_cache(maxsize=16)
+def _positions(key, device='cpu'):
+    counts = np.diff(np.frombuffer(key, dtype=np.int64))
+    if counts.size and int(counts.max()) > cfg.MAX_POSITIONS:
+        # transformer.py:40,51-52: the encoding table has 5000 rows
+        raise ValueError(
+            f'a segment of {int(counts.max())} positions exceeds the '
+            f'{cfg.MAX_POSITIONS}-entry positional encoding')
+    if not counts.size:
+        return torch.zeros(0, dtype=torch.int64, device=device)
+    return torch.from_numpy(np.concatenate(
+        [np.arange(count, dtype=np.int64) for count in counts])).to(device)
+
+
+class _Transformer(torch.nn.Module):
+    """`Transformer` (`transformer.py:13-30`): x + encoding[position in the
+    segment], then the layers (`model.layers.<i>`)."""
+
+    def __init__(self, config, prefix, state):
+        super().__init__()
+        self.model = torch.nn.Module()
+        self.model.layers = torch.nn.ModuleList(
+            _Layer(state, f'{prefix}.model.layers.{i}.')
+            for i in range(config.layers))
+        self.register_buffer('encoding', torch.from_numpy(
+            weights_module.positional_encoding(
+                cfg.MAX_POSITIONS, config.channels)).t().contiguous(),
+            persistent=False)
+
+    def forward(self, x, cu):
+        host = cu.detach().cpu().to(torch.int64).numpy()
+        index = _positions(np.ascontiguousarray(host).tobytes(), str(x.device))
+        x = x + self.encoding.index_select(1, index)
+        for layer in self.model.layers:
+            x = layer(x, cu)
+        return x
+
+
+class TransformerModel(torch.nn.Module):
+    """`TransformerModel(config, checkpoint=None, seed=0)`; `forward(features
+    [C_in, sum T], cu_frames, bounds [2, sum W], cu_words) -> logits [sum W]`,
+    the utterances back to back (`cu_*`: N + 1 prefix sums, on the host), as
+    `TorchModel`; `train.loss_fn` serves unchanged.
+
+    downsample_location 'intermediate' or 'loss', every downsample_method;
+    80 channels, 2 heads, no dropout (module docstring).  The parameters carry
+    the reference's names and order (`weights.parameter_shapes`):
+    `state_dict()` is read by `weights.load` and by every inference entry
+    point's `checkpoint=`.  Without a checkpoint they are bitwise
+    `initial_transformer_state(config, seed)`.  A segment longer than the
+    5000-entry positional encoding raises ValueError."""
+
+    def __init__(self, config=None, checkpoint=None, seed=0):
+        super().__init__()
+        self.config = config = config or api.active_config()
+        check_transformer_supported(config)
+        if checkpoint is None:
+            state = initial_transformer_state(config, seed)
+        else:
+            state = weights_module.load(checkpoint, config)
+        self.input_layer = _Parameters(
+            weight=state['input_layer.weight'], bias=state['input_layer.bias'])
+        self.frame_encoder = _Transformer(config, 'frame_encoder', state)
+        if config.has_decoder:
+            self.word_decoder = _Transformer(config, 'word_decoder', state)
+        self.output_layer = _Parameters(
+            weight=state['output_layer.weight'],
+            bias=state['output_layer.bias'])
+
+    def forward(self, features, cu_frames, bounds, cu_words):
+        conv = torch.ops.emphases_amd.conv1d_same_act
+        x = conv(features, self.input_layer.weight, self.input_layer.bias,
+                 cu_frames, 'none')
+        x = self.frame_encoder(x, cu_frames)
+        x = torch.ops.emphases_amd.segment_reduce(
+            x, bounds, cu_frames, cu_words, self.config.downsample_method)
+        if self.config.has_decoder:
+            x = self.word_decoder(x, cu_words)
+        x = conv(x, self.output_layer.weight, self.output_layer.bias,
+                 cu_words, 'none')
+        return x[0]

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 40
+#define EMPH_ABI_VERSION 41
 
 /* Segment-table fields */
 enum {
@@ -1393,6 +1393,59 @@ int emph_frame_head_backward(const float* dlogit, const float* h, int64_t ldh,
                              const int32_t* tiles, int32_t n_tiles, float* workspace,
                              float* dweight, float* dbias, float* dx, int64_t ld_dx,
                              void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* Transformer encoder layer under autograd                                  */
+/* ------------------------------------------------------------------------ */
+
+/* Backward of emph_attention with key_counts == NULL (the attention inside
+ * nn.MultiheadAttention, transformer.py:18-23, under autograd).  The scores
+ * are recomputed, never stored: with P = softmax(Q K^T / sqrt(d)), O = P V and
+ * D_i = sum_c dout[c][i] out[c][i] over the channels of the head,
+ *     dV = P^T dO     dS = P o (dO V^T - D)     dQ = dS K / sqrt(d)
+ *     dK = dS^T Q / sqrt(d)
+ *   qk, v, out  as emph_attention takes and leaves them ([2 channels, ld],
+ *               [ld, channels] position-major, [channels, ld])
+ *   dout  float32 [channels, ld]    gradient of `out`
+ *   dqkv  float32 [3 channels, ld]  channel-major, rows dQ | dK | dV: the
+ *               gradient of in_proj's output as ONE buffer
+ *   tiles the 64-wide tile table of the walked axis (tile_n = 64), frames or
+ *               words
+ *   workspace  emph_attention_backward_workspace(ld, heads) floats: the row
+ *               log-sum-exp (log2 units) and D, [2][heads][ld]
+ * Two launches: a pass per query tile (log-sum-exp and D into the workspace,
+ * then dQ) and a pass per key tile (dK, dV); all five products are fp32 MFMA.
+ * No atomics: every element of dqkv inside a segment is written by one lane
+ * in a fixed order, so the same inputs give the same bits.  Columns OUTSIDE
+ * the segments (the alignment gaps of the packed axis) are neither read nor
+ * written: dqkv keeps there what the caller put there.  Any segment length
+ * >= 1.  Only channels 80 in 2 heads (head dimension 40, transformer.py:20);
+ * any other shape returns EMPH_ERANGE and launches nothing. */
+int64_t emph_attention_backward_workspace(int64_t ld, int32_t heads);
+int emph_attention_backward(const float* qk, const float* v, const float* out,
+                            const float* dout, float* dqkv, int64_t ld, int32_t channels,
+                            int32_t heads, const int32_t* tiles, int32_t n_tiles,
+                            int32_t tile_n, float* workspace, void* stream);
+
+/* Backward of emph_add_layernorm (the post-LN residual under autograd).  `s`
+ * [channels, ld] is the pre-norm sum x + r, whose statistics are recomputed
+ * per column as the forward computes them (a constant column has
+ * rstd = 1 / sqrt(eps)); with xhat = (s - mean) rstd and g = dy gamma,
+ *     ds = rstd (g - mean_c(g) - xhat mean_c(g xhat))   (gradient of x AND r)
+ *     dgamma[c] = sum_t dy[c][t] xhat[c][t]             dbeta[c] = sum_t dy[c][t]
+ * over the columns inside the segments of the 64-wide tile table `tiles`
+ * (tile_n = 64) alone: ds is written there and nowhere else, and what lies
+ * between the segments reaches no sum.  Two launches: workgroup p of
+ * emph_add_layernorm_backward_parts(n_tiles) owns a fixed contiguous run of
+ * tiles and writes slab p of 2 channels floats into `workspace` (parts x 2
+ * channels floats); the second adds the slabs in a fixed order that depends
+ * on their number alone (no tiles: zeros).  No atomics.  channels 1..128;
+ * anything else returns EMPH_ERANGE and launches nothing. */
+int32_t emph_add_layernorm_backward_parts(int32_t n_tiles);
+int emph_add_layernorm_backward(const float* s, const float* gamma, const float* dy, float* ds,
+                                int64_t ld, int32_t channels, float eps, const int32_t* tiles,
+                                int32_t n_tiles, int32_t tile_n, float* workspace,
+                                float* dgamma, float* dbeta, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Measurement                                                               */

@@ -2,6 +2,9 @@
 PyTorch and against the fused trainer.
 
     python tools/ops_train_bench.py [--laps 7] [--seconds 1.0] [--out profiles/ops_train_step.json]
+    python tools/ops_train_bench.py --architecture transformer \
+        [--out profiles/ops_transformer_train_step.json] \
+        [--kernels-out profiles/attention_backward_kernels.json]
 
 The batch and the baselines are `tools/train_bench.py`'s: 75 utterances x
 1 000 frames x 30 words, default configuration, weights of `emphases.Model()`
@@ -19,6 +22,16 @@ A lap of one contender is timed with a pair of device events around `steps`
 steps, `steps` chosen so that a lap takes about `--seconds`; all are warmed up
 first (the ops' second step is the first on device-packed weights).
 Reported: median, minimum and maximum per-step time over the laps.
+
+`--architecture transformer`: the same batch through
+`emphases_amd.train.TransformerModel` (6 layers, 'intermediate': `ops`)
+against the same model as `torch.nn.TransformerEncoder(dropout=0.)` +
+autograd + Adam in float32 (`torch_fp32`), laps alternating.  `--kernels-out`
+adds the launch timer's per-kernel times of `emph_attention` and
+`emph_attention_backward` on one layer's shapes (75 x 1 000 positions, 2
+heads of 40), the MFMA flops they execute over the 157.3 TFLOP/s fp32 peak,
+and torch's own `scaled_dot_product_attention` forward and backward on the
+same shapes with the backend torch picked.
 """
 import argparse
 import json
@@ -37,13 +50,225 @@ import emphases_amd  # noqa: E402
 from emphases_amd import train  # noqa: E402
 
 
+PEAK_FP32_MFMA = 157.3e12
+
+
+class TorchTransformer(torch.nn.Module):
+    """`emphases.Model` under ARCHITECTURE 'transformer', 'intermediate' +
+    'sum', every dropout 0, on a batch of equal lengths (no padding mask)."""
+
+    def __init__(self, config, state):
+        super().__init__()
+        from emphases_amd import weights
+        stack = lambda: torch.nn.TransformerEncoder(  # noqa: E731
+            torch.nn.TransformerEncoderLayer(
+                80, 2, dim_feedforward=80, dropout=0.), config.layers,
+            enable_nested_tensor=False)
+        self.input_layer = torch.nn.Conv1d(80, 80, 3, padding='same')
+        self.frame_encoder = stack()
+        self.word_decoder = stack()
+        self.output_layer = torch.nn.Conv1d(80, 1, 3, padding='same')
+        self.register_buffer('encoding', torch.from_numpy(
+            weights.positional_encoding(1000, 80))[:, None], persistent=False)
+        self.load_state_dict(
+            {name.replace('.model.', '.'): torch.from_numpy(value)
+             for name, value in state.items()})
+
+    def forward(self, features, membership):
+        x = self.input_layer(features).permute(2, 0, 1)            # [T, B, C]
+        x = self.frame_encoder(x + self.encoding[:x.shape[0]])
+        words = torch.bmm(x.permute(1, 2, 0), membership)           # [B, C, W]
+        words = words.permute(2, 0, 1)
+        words = self.word_decoder(words + self.encoding[:words.shape[0]])
+        return self.output_layer(words.permute(1, 2, 0))
+
+
+def sdpa_backend(query, key, value):
+    """Which backend torch's dispatcher may pick for these tensors."""
+    try:
+        from torch.backends import cuda
+        parameters = cuda.SDPAParams(query, key, value, None, 0., False, False)
+        if cuda.flash_sdp_enabled() and cuda.can_use_flash_attention(parameters):
+            return 'flash'
+        if cuda.mem_efficient_sdp_enabled() and \
+                cuda.can_use_efficient_attention(parameters):
+            return 'mem_efficient'
+        return 'math'
+    except Exception as error:      # (the probe's signature moves between versions)
+        return f'unknown ({type(error).__name__})'
+
+
+def attention_kernels(path, items, frames):
+    """Per-kernel times of the attention forward and backward of one layer."""
+    from emphases_amd import ops, runtime
+    device = torch.device('cuda', 0)
+    layout = ops._layout(device, np.full(items, frames, dtype=np.int64))
+    ld = layout.plan.ld_frames
+    tiles, n_tiles = layout.tiles(64)
+    generator = torch.Generator(device='cuda').manual_seed(0)
+    qk = torch.randn(160, ld, device=device, generator=generator)
+    v = torch.randn(ld, 80, device=device, generator=generator)
+    dout = torch.randn(80, ld, device=device, generator=generator)
+    out = torch.zeros(80, ld, device=device)
+    dqkv = torch.zeros(240, ld, device=device)
+    lib = runtime.library()
+    workspace = torch.empty(
+        int(lib.emph_attention_backward_workspace(ld, 2)), device=device)
+    times = {'emph_attention': [], 'backward_queries': [], 'backward_keys': []}
+    for lap in range(8):
+        with runtime.LaunchTimer() as timer:
+            runtime.check(lib.emph_attention(
+                qk.data_ptr(), v.data_ptr(), out.data_ptr(), ld, 80, 2,
+                tiles.data_ptr(), n_tiles, 64, None, runtime.stream()),
+                'emph_attention')
+            runtime.check(lib.emph_attention_backward(
+                qk.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                dqkv.data_ptr(), ld, 80, 2, tiles.data_ptr(), n_tiles, 64,
+                workspace.data_ptr(), runtime.stream()),
+                'emph_attention_backward')
+        if lap:                                     # (the first lap warms up)
+            for name, value in zip(times, timer.microseconds):
+                times[name].append(float(value))
+    blocks = items * 2 * ((frames + 15) // 16) ** 2  # 16 x 16 score blocks
+    mfma = 2 * 16 * 16 * 4                           # flops of one 16x16x4
+    flops = {'emph_attention': blocks * 22 * mfma,
+             'backward_queries': blocks * (10 + 20 + 12) * mfma,
+             'backward_keys': blocks * (20 + 24) * mfma}
+    record = {'shape': {'utterances': items, 'positions': frames, 'heads': 2,
+                        'head_dimension': 40},
+              'device': torch.cuda.get_device_name(0), 'kernels': {}}
+    for name, values in times.items():
+        median = float(np.median(values))
+        record['kernels'][name] = {
+            'us_median': median, 'us_laps': values,
+            'executed_mfma_flops': flops[name],
+            'fraction_of_fp32_mfma_peak':
+                flops[name] / (median * 1e-6) / PEAK_FP32_MFMA}
+    record['kernels']['emph_attention_backward'] = {
+        'us_median': record['kernels']['backward_queries']['us_median'] +
+        record['kernels']['backward_keys']['us_median'],
+        'executed_mfma_flops':
+            flops['backward_queries'] + flops['backward_keys']}
+    total = record['kernels']['emph_attention_backward']
+    total['fraction_of_fp32_mfma_peak'] = total['executed_mfma_flops'] / (
+        total['us_median'] * 1e-6) / PEAK_FP32_MFMA
+    # torch's own attention on the same shapes: [B, heads, T, d] float32
+    query, key, value = (torch.randn(
+        items, 2, frames, 40, device=device, generator=generator
+    ).requires_grad_(True) for _ in range(3))
+    upstream = torch.randn(items, 2, frames, 40, device=device,
+                           generator=generator)
+    attention = torch.nn.functional.scaled_dot_product_attention
+    forward, backward = [], []
+    for lap in range(8):
+        events = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        events[0].record()
+        result = attention(query, key, value)
+        events[1].record()
+        result.backward(upstream)
+        events[2].record()
+        events[2].synchronize()
+        query.grad = key.grad = value.grad = None
+        if lap:
+            forward.append(events[0].elapsed_time(events[1]) * 1e3)
+            backward.append(events[1].elapsed_time(events[2]) * 1e3)
+    record['torch_sdpa'] = {
+        'backend': sdpa_backend(query, key, value),
+        'forward_us_median': float(np.median(forward)),
+        'backward_us_median': float(np.median(backward)),
+        'forward_us_laps': forward, 'backward_us_laps': backward,
+        'note': 'device events around the call: launches included'}
+    print(json.dumps(record))
+    with open(path, 'w') as file:
+        json.dump(record, file, indent=1)
+        file.write('\n')
+
+
+def transformer_main(arguments):
+    torch.cuda.set_device(0)
+    batch = train_bench.make_batch()
+    features, _, bounds, _, targets = batch
+    items, frames, words = \
+        train_bench.ITEMS, train_bench.FRAMES, train_bench.WORDS
+    config = emphases_amd.Config(architecture='transformer', layers=6)
+    state = train.initial_transformer_state(config, seed=0)
+    model = train.TransformerModel(config, checkpoint=state).cuda()
+    optimizer = torch.optim.Adam(model.parameters())
+    flat = (features.permute(1, 0, 2).reshape(80, items * frames).cuda(),
+            torch.arange(items + 1) * frames,
+            bounds.permute(1, 0, 2).reshape(2, items * words),
+            torch.arange(items + 1) * words)
+    flat_targets = targets.reshape(items * words).cuda()
+
+    def ops_step():
+        optimizer.zero_grad(set_to_none=True)
+        loss = train.loss_fn(model(*flat), flat_targets, 'bce')
+        loss.backward()
+        optimizer.step()
+        return loss.detach()
+
+    device_features, device_bounds, device_targets = \
+        features.cuda(), bounds.cuda(), targets.cuda()
+    frame = torch.arange(frames, device='cuda')[None, :, None]
+    membership = ((frame >= device_bounds[:, 0, None, :]) &
+                  (frame < device_bounds[:, 1, None, :])).float()
+    plain = TorchTransformer(config, state).cuda()
+    plain.train()
+    plain_optimizer = torch.optim.Adam(plain.parameters())
+    contenders = {
+        'ops': ops_step,
+        'torch_fp32': lambda: train_bench.torch_step(
+            plain, plain_optimizer, None, device_features, membership,
+            device_targets)}
+    first = {}
+    for name, function in contenders.items():
+        first[name] = float(function().detach())
+        for _ in range(2):
+            function()
+    torch.cuda.synchronize()
+    steps = {}
+    for name, function in contenders.items():
+        probe = train_bench.timed(function, 2)
+        steps[name] = arguments.steps or max(
+            2, int(arguments.seconds * 1e3 / probe))
+    laps = {name: [] for name in contenders}
+    for _ in range(arguments.laps):
+        for name, function in contenders.items():
+            laps[name].append(train_bench.timed(function, steps[name]))
+    record = {
+        'architecture': 'transformer', 'layers': config.layers,
+        'downsample_location': config.downsample_location,
+        'batch': {'utterances': items, 'frames': frames, 'words': words},
+        'device': torch.cuda.get_device_name(0),
+        'laps': arguments.laps, 'steps_per_lap': steps, 'first_loss': first,
+        'ms_per_step': {
+            name: {'median': float(np.median(values)),
+                   'min': float(np.min(values)), 'max': float(np.max(values))}
+            for name, values in laps.items()},
+        'ms_per_step_laps': laps}
+    median = {name: record['ms_per_step'][name]['median'] for name in laps}
+    record['torch_fp32_over_ops'] = median['torch_fp32'] / median['ops']
+    print(json.dumps(record))
+    if arguments.out:
+        with open(arguments.out, 'w') as file:
+            json.dump(record, file, indent=1)
+            file.write('\n')
+    if arguments.kernels_out:
+        attention_kernels(arguments.kernels_out, items, frames)
+
+
 def main():
     parser = argparse.ArgumentParser()
+    parser.add_argument('--architecture', default='convolution',
+                        choices=('convolution', 'transformer'))
+    parser.add_argument('--kernels-out', default=None)
     parser.add_argument('--laps', type=int, default=7)
     parser.add_argument('--seconds', type=float, default=1.0)
     parser.add_argument('--steps', type=int, default=None)
     parser.add_argument('--out', default=None)
     arguments = parser.parse_args()
+    if arguments.architecture == 'transformer':
+        return transformer_main(arguments)
     torch.cuda.set_device(0)
     batch = train_bench.make_batch()
     features, _, bounds, _, targets = batch
