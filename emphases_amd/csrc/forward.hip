@@ -75,9 +75,10 @@ int emph_prominence_forward(const emph_conv_model* model, const void* audio,
                  "emph_prominence_forward: word_sums needs conv_variant 1 and a sum / average "
                  "reduction");
 
-    int status = emph_logmel(audio, audio_format, seg, frontend_tiles, n_frontend_tiles, m.table,
-                             m.mel_start, m.mel_count, m.mel_offset, m.mel_values, m.mel_nnz,
-                             features, ld_frames, 0, -1, nullptr, nullptr, m.normalize, stream);
+    int status = emph_logmel_planned(audio, audio_format, seg, frontend_tiles, n_frontend_tiles,
+                                     m.table, m.mel_start, m.mel_count, m.mel_offset,
+                                     m.mel_values, m.mel_nnz, m.mel_plan, features, ld_frames, 0,
+                                     -1, nullptr, nullptr, m.normalize, stream);
     if (status) return status;
     auto conv = [&](const float* in, float* out, const float* pack, const float* bias, int c_in,
                     int activation) {

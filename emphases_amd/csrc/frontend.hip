@@ -20,11 +20,13 @@
 // points per lane - three radix-8 passes in registers with two wave-private LDS
 // transposes - followed by the real-FFT split on bin pairs (only the high half
 // of the spectrum crosses lanes), magnitudes, the 1001-non-zero sparse mel
-// projection and the log.  The wave's [80 x 8] result tile is staged in LDS and
+// projection (dealt evenly over the lanes by a host-built plan: kQuads below)
+// and the log.  The wave's [80 x 8] result tile is staged in LDS and
 // written as 32-byte row segments.  There is no workgroup barrier anywhere, and
 // nothing of the 513 x F complex spectrogram ever reaches HBM.
 #include <math.h>
 #include <stdarg.h>
+#include <string.h>
 
 #include "common.h"
 
@@ -78,8 +80,34 @@ __device__ __forceinline__ int spectrum_slot(int k) { return k + 4 * (k >> 5); }
 constexpr int kHighBase = 256 + 4 * (256 >> 5);   // slot of bin 256: only 256..511 are stored
 constexpr int kMagFloats = 560;      // 513 magnitudes + zero tail for the runs, laid over
                                      // the frame's exchange buffer
-// floats of LDS per wave: exchange buffers, output tile, loudness tile
-constexpr int kWaveFloats = kPair * kExFloats + kMels * kTileStride + kWaveFrames;
+// Balanced mel projection (QUADS): the filterbank as a list of (row, 16-byte
+// quad of the magnitude buffer) pieces in row order, dealt to the lanes in
+// consecutive runs of at most kQuads.  A lane sums consecutive quads of one row
+// in order and stores every such partial at a fixed slot [row][k], k = index of
+// the lane among the lanes that hold pieces of that row (at most kPartSlots);
+// one lane per row then adds the four slots in order.  No atomics: a row's
+// value is the same bits wherever its frame sits.  The slots have LDS of their
+// own: the ones no lane owns are zeroed once per kernel and stay zero, and a
+// quad that does not end a partial stores to the lane's own spare word.
+constexpr int kQuads = 5;
+constexpr int kPartSlots = 4;
+constexpr int kPartSpare = kMels * kPartSlots;             // [64] one spare word per lane
+constexpr int kPartFloats = kPartSpare + 64;
+// floats of LDS per wave: exchange buffers, output tile, loudness tile, partials
+// (4 waves x 10 080 bytes, + 2 064 with loudness: three workgroups are 127 KB of
+// a CU's 160 KB)
+constexpr int kWaveFloats =
+    kPair * kExFloats + kMels * kTileStride + kWaveFrames + kPartFloats;
+static_assert(kWaveFloats % 4 == 0 && (kWaveFloats - kPartFloats) % 4 == 0,
+              "the partial slots are read 16 bytes at a time");
+// Plan of the balanced projection, 32-bit words [item][lane]
+// (emph_frontend_mel_plan_fill):
+constexpr int kPlanRead = 0;                               // [kQuads] float index of the quad
+constexpr int kPlanWrite = kPlanRead + kQuads * 64;        // [kQuads] float index in the partials
+constexpr int kPlanWeight = kPlanWrite + kQuads * 64;      // [4 kQuads] float weights
+constexpr int kPlanRestart = kPlanWeight + 4 * kQuads * 64;   // bit j: quad j opens another row
+constexpr int kPlanTail = kPlanRestart + 64;    // [0]: some quad reads past bin 512
+constexpr int kPlanSize = kPlanTail + 64;
 // Filterbank runs are read from LDS as 16-byte pieces from a start rounded down
 // to a multiple of four bins: rows 0..63 (at most 20 bins + 3 of alignment) as
 // six pieces by one lane each, rows 64..79 (at most 40 + 3) as three pieces by
@@ -347,14 +375,18 @@ __device__ __forceinline__ void load_edge(const Chunk& chunk, int frame, int p, 
 // time (kPair = 2 lets one frame's arithmetic cover the other's LDS round trips
 // at 253 VGPRs; kPair = 1 at 164 VGPRs puts three waves on a SIMD instead and is
 // what ships: 66.5 vs 68.7 us).
-template <int MODE, bool PCM>
+//
+// QUADS: the mel projection dealt evenly over the lanes by `mel_plan` (above);
+// otherwise one lane per row for rows 0..63 and four per row for rows 64..79.
+template <int MODE, bool PCM, bool QUADS>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, kWavesPerSimd))) void frontend_kernel(
     const void* __restrict__ audio, const int64_t* __restrict__ seg,
     const int32_t* __restrict__ tiles, const float* __restrict__ table,
     const int32_t* __restrict__ mel_start, const int32_t* __restrict__ mel_count,
     const int32_t* __restrict__ mel_offset, const float* __restrict__ mel_values,
-    int mel_nnz, float* __restrict__ out, int64_t ld, int mel_row, int loud_row,
+    int mel_nnz, const uint32_t* __restrict__ mel_plan, float* __restrict__ out, int64_t ld,
+    int mel_row, int loud_row,
     float* __restrict__ seg_peak, const float* __restrict__ a_weights,
     int normalize, int n_tiles) {
     constexpr bool kMel = MODE == 0 || MODE == 2;
@@ -372,6 +404,7 @@ __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, kWavesPerSimd))) void frontend
     float* exchange = mine;                                  // [kPair][kExFloats]
     float* tile = exchange + kPair * kExFloats;              // [80][kTileStride]
     float* loud_tile = tile + kMels * kTileStride;           // [kWaveFrames]
+    float* parts = loud_tile + kWaveFrames;                  // [80][kPartSlots] + [64] (QUADS)
     float* weights = lds + 4 * kWaveFloats;                  // [513+] (loudness only)
 
     if (kLoud) {
@@ -417,7 +450,33 @@ __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, kWavesPerSimd))) void frontend
     // that the per-frame loops are fully unrolled with every LDS read independent.
     float weight_a[kRunA], weight_b[kRunB];
     int start_a = 0, start_b = 0;
-    if (kMel) {
+    // QUADS: the lane's kQuads quads - where each is read, its four weights,
+    // where its running sum is stored, and (a lane mask, held in scalar
+    // registers) whether it opens another row, that is restarts the sum
+    float quad_weight[4 * kQuads];
+    int quad_read[kQuads], quad_write[kQuads];
+    uint64_t quad_restart[kQuads];
+    // does any read go past bin 512?  (no quad of the bundled basis does: its
+    // Nyquist column is empty)
+    bool zero_tail = true;
+    if (kMel && QUADS) {
+        zero_tail = __builtin_amdgcn_readfirstlane(static_cast<int>(mel_plan[kPlanTail])) != 0;
+        const uint32_t restarts = mel_plan[kPlanRestart + lane];
+#pragma unroll
+        for (int j = 0; j < kQuads; ++j) {
+            quad_read[j] = static_cast<int>(mel_plan[kPlanRead + 64 * j + lane]);
+            quad_write[j] = static_cast<int>(mel_plan[kPlanWrite + 64 * j + lane]);
+            quad_restart[j] = __builtin_amdgcn_ballot_w64(((restarts >> j) & 1u) != 0);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                quad_weight[4 * j + i] =
+                    __uint_as_float(mel_plan[kPlanWeight + 64 * (4 * j + i) + lane]);
+        }
+        // the slots no lane stores to stay zero for the kernel's whole life
+#pragma unroll
+        for (int index = lane; index < kPartFloats; index += 64) parts[index] = 0.f;
+        frontend_fence();
+    } else if (kMel) {
         const int first_a = mel_start[lane];
         const int count_a = mel_count[lane];
         const int offset_a = mel_offset[lane];
@@ -649,11 +708,51 @@ __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, kWavesPerSimd))) void frontend
                     mag[256] = __builtin_amdgcn_sqrtf(power[f][8] + (1e-6f - kPowerFloor));
                 // zero tail: the fixed-length runs read past bin 512 (weight 0, but
                 // the buffer holds spectrum bits there: 0 * NaN would poison the sum)
-                if (lane < kMagFloats - kBins) mag[kBins + lane] = 0.f;
+                if (zero_tail && lane < kMagFloats - kBins) mag[kBins + lane] = 0.f;
             }
             frontend_fence();
 #pragma unroll
-            for (int f = 0; f < kPair; ++f) {
+            for (int f = 0; f < (QUADS ? kPair : 0); ++f) {
+                const float* mag = exchange + f * kExFloats;
+                const int column = min(local + f, valid - 1);
+                float acc = 0.f;
+                // every read in front of the first store: independent, all in flight
+                float4 four[kQuads];
+#pragma unroll
+                for (int j = 0; j < kQuads; ++j)
+                    four[j] = *reinterpret_cast<const float4*>(mag + quad_read[j]);
+#pragma unroll
+                for (int j = 0; j < kQuads; ++j) {
+                    // another row: the sum starts again (one v_cndmask on a scalar mask)
+                    if (j)
+                        asm("v_cndmask_b32_e64 %0, %1, 0, %2"
+                            : "=v"(acc) : "v"(acc), "s"(quad_restart[j]));
+                    acc = fmaf(quad_weight[4 * j], four[j].x, acc);
+                    acc = fmaf(quad_weight[4 * j + 1], four[j].y, acc);
+                    acc = fmaf(quad_weight[4 * j + 2], four[j].z, acc);
+                    acc = fmaf(quad_weight[4 * j + 3], four[j].w, acc);
+                    parts[quad_write[j]] = acc;     // slot [row][k], or the lane's spare word
+                }
+                frontend_fence();
+                // row `lane`, then row 64 + lane: the four slots in a fixed order
+#pragma unroll
+                for (int pass = 0; pass < 2; ++pass) {
+                    const int m = 64 * pass + lane;
+                    if (m < kMels) {
+                        const float4 slot =
+                            *reinterpret_cast<const float4*>(parts + kPartSlots * m);
+                        const float sum = ((slot.x + slot.y) + slot.z) + slot.w;
+                        // natural log on v_log_f32 (log2, 1 ulp; the argument is >= 1e-5);
+                        // (x + 10) / 10 as one fma: both within 1e-7 of the exact forms
+                        float value = kLn2 * __builtin_amdgcn_logf(fmaxf(sum, 1e-5f));
+                        if (normalize) value = fmaf(value, 0.1f, 1.f);
+                        tile[m * kTileStride + column] = value;
+                    }
+                }
+                frontend_fence();      // the next frame's partials come after these reads
+            }
+#pragma unroll
+            for (int f = 0; f < (QUADS ? 0 : kPair); ++f) {
                 const float* mag = exchange + f * kExFloats;
                 const int column = min(local + f, valid - 1);
                 float acc = 0.f;
@@ -778,6 +877,185 @@ int emph_frontend_table_fill(float* host_table) {
     return EMPH_OK;
 }
 
+int64_t emph_frontend_mel_plan_size(void) { return kPlanSize; }
+
+int emph_frontend_mel_plan_fill(const int32_t* mel_start, const int32_t* mel_count,
+                                const int32_t* mel_offset, const float* mel_values,
+                                int32_t mel_nnz, uint32_t* host_plan, int32_t* counts) {
+    EMPH_REQUIRE(mel_start && mel_count && mel_offset && mel_values && host_plan, EMPH_EINVAL,
+                 "emph_frontend_mel_plan_fill: null pointer");
+    // the pieces: every row's non-zeros, widened to 16-byte quads of the magnitudes
+    struct Piece {
+        int row, bin;
+        float weight[4];
+    };
+    static_assert(kPartSlots == 4, "a row's slots are one 16-byte read");
+    constexpr int kMost = 64 * kQuads;
+    Piece pieces[kMost];
+    int n = 0;
+    for (int row = 0; row < kMels; ++row) {
+        const int start = mel_start[row], count = mel_count[row], offset = mel_offset[row];
+        EMPH_REQUIRE(start >= 0 && count >= 0 && start + count <= kBins && offset >= 0 &&
+                         offset + count <= mel_nnz,
+                     EMPH_EINVAL, "emph_frontend_mel_plan_fill: row %d: run [%d, %d) at %d of %d",
+                     row, start, start + count, offset, mel_nnz);
+        int low = 0, high = count;         // a run may be padded with explicit zeros
+        while (low < high && mel_values[offset + low] == 0.f) ++low;
+        while (high > low && mel_values[offset + high - 1] == 0.f) --high;
+        if (low == high) continue;         // an empty row: its slots stay zero
+        const int first = start + low, last = start + high - 1;
+        for (int bin = first & ~3; bin <= last; bin += 4) {
+            EMPH_REQUIRE(n < kMost, EMPH_ERANGE,
+                         "emph_frontend_mel_plan_fill: the basis has more than %d quads "
+                         "(%d per lane)", kMost, kQuads);
+            Piece& piece = pieces[n++];
+            piece.row = row;
+            piece.bin = bin;
+            for (int i = 0; i < 4; ++i)
+                piece.weight[i] = bin + i >= first && bin + i <= last
+                                      ? mel_values[offset + bin + i - start] : 0.f;
+        }
+    }
+    static_assert(((kBins - 1) | 3) < kMagFloats, "a quad stays inside the magnitude buffer");
+    // Consecutive runs of the list, one per lane: a run takes quads while it has
+    // fewer than kQuads and the next one would not open its fourth partial
+    // (`most` 3); when 64 such runs do not hold the list, even runs of
+    // ceil(n / 64) quads, whatever their partials.
+    int begin_of[65];
+    int most_quads = 0;
+    for (int most = 3; most <= kQuads; most += kQuads - 3) {
+        int at = 0;
+        most_quads = 0;
+        for (int run = 0; run < 64; ++run) {
+            begin_of[run] = at;
+            int partials = 0;
+            const int even = most == kQuads ? (n + 63) / 64 : kQuads;
+            while (at < n && at - begin_of[run] < even) {
+                const bool opens = at == begin_of[run] || pieces[at].row != pieces[at - 1].row;
+                if (opens && partials == most) break;
+                partials += opens;
+                ++at;
+            }
+            if (at - begin_of[run] > most_quads) most_quads = at - begin_of[run];
+        }
+        begin_of[64] = at;
+        if (at == n) break;
+    }
+    // Which lane takes which run is free (a row's slots follow the order of the
+    // list, not of the lanes): chosen so that the sixteen lanes the LDS serves
+    // together for a 16-byte read (MI355X_MICROARCH.md, LDS table) hit sixteen
+    // different bank quads, or the same address.  Swaps of two lanes of
+    // different groups that do not raise the cycle count, a fixed number of them
+    // from a fixed seed: the plan of a basis is always the same plan.
+    auto chunk_of = [&](int run, int j) {
+        const int mine = begin_of[run + 1] - begin_of[run];
+        return mine ? pieces[begin_of[run] + (j < mine ? j : mine - 1)].bin >> 2 : 0;
+    };
+    auto group_of = [](int lane) {
+        const int low = lane & 31;
+        const bool first = low < 4 || (low >= 12 && low < 16) || (low >= 20 && low < 28);
+        return 2 * (lane >> 5) + (first ? 0 : 1);
+    };
+    int run_of[64];
+    for (int lane = 0; lane < 64; ++lane) run_of[lane] = lane;
+    auto cycles_of = [&](int group) {
+        int cycles = 0;
+        for (int j = 0; j < kQuads; ++j) {
+            int chunks[16], count = 0, worst = 0;
+            for (int lane = 0; lane < 64; ++lane)
+                if (group_of(lane) == group) chunks[count++] = chunk_of(run_of[lane], j);
+            for (int a = 0; a < count; ++a) {
+                int same_bank = 1;       // distinct addresses on chunk a's bank quad
+                for (int c = 0; c < count; ++c) {
+                    if ((chunks[c] & 15) != (chunks[a] & 15) || chunks[c] == chunks[a]) continue;
+                    bool seen = false;
+                    for (int d = 0; d < c; ++d) seen = seen || chunks[d] == chunks[c];
+                    same_bank += !seen;
+                }
+                if (same_bank > worst) worst = same_bank;
+            }
+            cycles += worst;
+        }
+        return cycles;
+    };
+    int cycles[4];
+    for (int group = 0; group < 4; ++group) cycles[group] = cycles_of(group);
+    uint32_t state = 12345u;
+    for (int trial = 0; trial < 40000; ++trial) {
+        state = state * 1103515245u + 12345u;
+        const int a = (state >> 8) & 63;
+        state = state * 1103515245u + 12345u;
+        const int c = (state >> 8) & 63;
+        const int ga = group_of(a), gc = group_of(c);
+        if (ga == gc) continue;
+        if (cycles[0] + cycles[1] + cycles[2] + cycles[3] == 4 * kQuads) break;
+        int swap = run_of[a];
+        run_of[a] = run_of[c];
+        run_of[c] = swap;
+        const int now_a = cycles_of(ga), now_c = cycles_of(gc);
+        if (now_a + now_c <= cycles[ga] + cycles[gc]) {
+            cycles[ga] = now_a;
+            cycles[gc] = now_c;
+        } else {
+            run_of[c] = run_of[a];
+            run_of[a] = swap;
+        }
+    }
+    int lane_of[64];
+    for (int lane = 0; lane < 64; ++lane) lane_of[run_of[lane]] = lane;
+    // the kernel zeroes the magnitudes' tail only for a quad that reads it
+    bool tail = false;
+    for (int index = 0; index < n; ++index) tail = tail || pieces[index].bin + 3 >= kBins;
+    for (int index = 0; index < 64; ++index) host_plan[kPlanTail + index] = tail;
+    int row_lanes[kMels] = {0};
+    int most_partials = 0, most_lanes = 0;
+    for (int run = 0; run < 64; ++run) {
+        const int lane = lane_of[run];
+        const int begin = begin_of[run];
+        const int mine = begin_of[run + 1] - begin;
+        uint32_t restarts = 0;
+        int partials = 0;
+        for (int j = 0; j < kQuads; ++j) {
+            // past the lane's last quad: the same row again with zero weights, so
+            // that a lane's last partial always ends at quad kQuads - 1
+            const bool live = j < mine;
+            const Piece* piece = mine ? &pieces[begin + (live ? j : mine - 1)] : nullptr;
+            host_plan[kPlanRead + 64 * j + lane] = piece ? piece->bin : 0;
+            for (int i = 0; i < 4; ++i) {
+                const float weight = live ? piece->weight[i] : 0.f;
+                uint32_t bits;
+                memcpy(&bits, &weight, sizeof(bits));
+                host_plan[kPlanWeight + 64 * (4 * j + i) + lane] = bits;
+            }
+            if (live && j > 0 && piece->row != pieces[begin + j - 1].row) restarts |= 1u << j;
+            const bool closes = mine && (j == kQuads - 1 ||
+                                         (j + 1 < mine && pieces[begin + j + 1].row != piece->row));
+            int where = kPartSpare + lane;
+            if (closes) {
+                const int slot = row_lanes[piece->row]++;
+                EMPH_REQUIRE(slot < kPartSlots, EMPH_ERANGE,
+                             "emph_frontend_mel_plan_fill: row %d is spread over more than "
+                             "%d lanes", piece->row, kPartSlots);
+                where = kPartSlots * piece->row + slot;
+                ++partials;
+            }
+            host_plan[kPlanWrite + 64 * j + lane] = where;
+        }
+        host_plan[kPlanRestart + lane] = restarts;
+        if (partials > most_partials) most_partials = partials;
+    }
+    for (int row = 0; row < kMels; ++row)
+        if (row_lanes[row] > most_lanes) most_lanes = row_lanes[row];
+    if (counts) {
+        counts[0] = n;
+        counts[1] = most_quads;
+        counts[2] = most_partials;
+        counts[3] = most_lanes;
+        counts[4] = cycles[0] + cycles[1] + cycles[2] + cycles[3];
+    }
+    return EMPH_OK;
+}
+
 int emph_logmel(const void* audio, int32_t audio_format, const int64_t* seg,
                 const int32_t* tiles, int32_t n_tiles, const float* table,
                 const int32_t* mel_start, const int32_t* mel_count,
@@ -785,6 +1063,18 @@ int emph_logmel(const void* audio, int32_t audio_format, const int64_t* seg,
                 float* out, int64_t ld, int32_t mel_row, int32_t loud_row,
                 const float* seg_peak, const float* a_weights, int32_t normalize,
                 void* stream) {
+    return emph_logmel_planned(audio, audio_format, seg, tiles, n_tiles, table, mel_start,
+                               mel_count, mel_offset, mel_values, mel_nnz, nullptr, out, ld,
+                               mel_row, loud_row, seg_peak, a_weights, normalize, stream);
+}
+
+int emph_logmel_planned(const void* audio, int32_t audio_format, const int64_t* seg,
+                        const int32_t* tiles, int32_t n_tiles, const float* table,
+                        const int32_t* mel_start, const int32_t* mel_count,
+                        const int32_t* mel_offset, const float* mel_values, int32_t mel_nnz,
+                        const uint32_t* mel_plan, float* out, int64_t ld, int32_t mel_row,
+                        int32_t loud_row, const float* seg_peak, const float* a_weights,
+                        int32_t normalize, void* stream) {
     if (n_tiles == 0) return EMPH_OK;
     const bool mel = mel_row >= 0, loud = loud_row >= 0;
     EMPH_REQUIRE(audio && seg && tiles && table && out, EMPH_EINVAL,
@@ -802,23 +1092,29 @@ int emph_logmel(const void* audio, int32_t audio_format, const int64_t* seg,
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* peak = const_cast<float*>(seg_peak);
     const bool pcm = audio_format == EMPH_AUDIO_PCM16;
-#define EMPH_FRONTEND(MODE, PCM)                                                          \
+#define EMPH_FRONTEND(MODE, PCM, QUADS)                                                   \
     do {                                                                                  \
-        auto kernel = frontend_kernel<MODE, PCM>;                                         \
+        auto kernel = frontend_kernel<MODE, PCM, QUADS>;                                       \
         static LdsReservation reserved;                                                   \
         if (int status = reserve_lds(reserved, reinterpret_cast<const void*>(kernel),     \
                                      lds, "emph_logmel"))                                 \
             return status;                                                                \
         EMPH_LAUNCH(kernel, dim3(frontend_grid(n_tiles)), dim3(256), lds, s, audio, seg,  \
                     tiles, table, mel_start, mel_count, mel_offset, mel_values, mel_nnz,  \
-                    out, ld, mel_row, loud_row, peak, a_weights, normalize, n_tiles);     \
+                    mel_plan, out, ld, mel_row, loud_row, peak, a_weights, normalize,     \
+                    n_tiles);                                                             \
     } while (0)
-    if (mel && loud) {
-        if (pcm) EMPH_FRONTEND(2, true); else EMPH_FRONTEND(2, false);
+    // without a plan (or a basis that has none): one lane per row
+    if (mel && loud && mel_plan) {
+        if (pcm) EMPH_FRONTEND(2, true, true); else EMPH_FRONTEND(2, false, true);
+    } else if (mel && loud) {
+        if (pcm) EMPH_FRONTEND(2, true, false); else EMPH_FRONTEND(2, false, false);
+    } else if (mel && mel_plan) {
+        if (pcm) EMPH_FRONTEND(0, true, true); else EMPH_FRONTEND(0, false, true);
     } else if (mel) {
-        if (pcm) EMPH_FRONTEND(0, true); else EMPH_FRONTEND(0, false);
+        if (pcm) EMPH_FRONTEND(0, true, false); else EMPH_FRONTEND(0, false, false);
     } else {
-        if (pcm) EMPH_FRONTEND(3, true); else EMPH_FRONTEND(3, false);
+        if (pcm) EMPH_FRONTEND(3, true, false); else EMPH_FRONTEND(3, false, false);
     }
     return check_launch("emph_logmel");
 }
@@ -841,8 +1137,10 @@ int emph_frontend_peak(const void* audio, int32_t audio_format, const int64_t* s
     float* out = nullptr;
     float* peak = seg_peak;
     const int64_t ld = 0;
+    const uint32_t* mel_plan = nullptr;
     const int mel_nnz = 0, mel_row = -1, loud_row = -1, normalize = 0;
-    if (audio_format == EMPH_AUDIO_PCM16) EMPH_FRONTEND(1, true); else EMPH_FRONTEND(1, false);
+    if (audio_format == EMPH_AUDIO_PCM16) EMPH_FRONTEND(1, true, false);
+    else EMPH_FRONTEND(1, false, false);
     return check_launch("emph_frontend_peak");
 }
 #undef EMPH_FRONTEND

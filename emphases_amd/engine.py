@@ -116,6 +116,16 @@ def check_supported(config):
                 "wide for the fused word stage's 64-word window")
 
 
+@functools.lru_cache(maxsize=None)
+def _default_mel_plan():
+    """The balanced mel projection of the default basis (host, uint32), or
+    None: built once per process (the placement of the lanes is a search)."""
+    basis = melbasis.default()
+    plan, _ = runtime.frontend_mel_plan(
+        basis.row_start, basis.row_count, basis.row_offset, basis.values)
+    return plan
+
+
 def a_weighting():
     """A-weighting minus REF_DB on the 8 kHz / 1024-bin grid the reference
     evaluates it on (`loudness.py:110-120`; librosa.A_weighting restated from
@@ -221,6 +231,23 @@ class Engine:
         self.mel_offset = to(basis.row_offset)
         self.mel_values = to(basis.values)
         self.mel_nnz = int(basis.values.size)
+        # the projection dealt evenly over the lanes (csrc/frontend.hip:
+        # kQuads); EMPHASES_MEL_PLAN=0, or a basis that does not fit: one lane
+        # per row.  Like the composed first conv layer (below) only for the
+        # conv model in front of a per-word sum or average: the mapping adds a
+        # row's products in another order, as accurate against float64 as the
+        # old one (worst 4.28e-6 both), but 'max' / 'center' hand single
+        # frames on and the Transformer amplifies a last digit, and
+        # tests/test_gpu_paths.py pins those rows to what was measured
+        # (conv_max: 2.87e-6 of the 3e-6 that precision='bf16x6' promises,
+        # 3.44e-6 with the plan; tf_64x2: 5.6e-6 where 4.4e-6 +- 10 % is held)
+        self.mel_plan = None
+        if os.environ.get('EMPHASES_MEL_PLAN', '1') != '0' and \
+                config.architecture == 'convolution' and \
+                config.downsample_method in ('sum', 'average'):
+            mel_plan = _default_mel_plan()
+            self.mel_plan = None if mel_plan is None else \
+                to(mel_plan.view(np.int32))
         self.a_weights = to(a_weighting())
 
         # Model
@@ -397,7 +424,8 @@ class Engine:
             decoder_biases=pointer(self.decoder_biases),
             out_weight=pointer(self.output_weight),
             out_bias=pointer(self.output_bias),
-            compose=pointer(self._compose_pack if self.stack else None))
+            compose=pointer(self._compose_pack if self.stack else None),
+            mel_plan=pointer(self.mel_plan))
 
     def _stack(self, prefix):
         config, state, dev = self.config, self.state, self.device
@@ -802,13 +830,14 @@ class Engine:
                     runtime.stream()), 'emph_frontend_peak')
         if mel_row >= 0 or loud_row >= 0:
             with self._timed('frontend_logmel'):
-                runtime.check(self.lib.emph_logmel(
+                runtime.check(self.lib.emph_logmel_planned(
                     audio.data_ptr(), audio_format(audio), table.data_ptr(),
                     tiles.data_ptr(),
                     count, self.table.data_ptr(), self.mel_start.data_ptr(),
                     self.mel_count.data_ptr(), self.mel_offset.data_ptr(),
-                    self.mel_values.data_ptr(), self.mel_nnz, out.data_ptr(),
-                    plan.ld_frames, mel_row, loud_row,
+                    self.mel_values.data_ptr(), self.mel_nnz,
+                    None if self.mel_plan is None else self.mel_plan.data_ptr(),
+                    out.data_ptr(), plan.ld_frames, mel_row, loud_row,
                     None if peak is None else peak.data_ptr(),
                     self.a_weights.data_ptr(), int(config.normalize),
                     runtime.stream()), 'emph_logmel')

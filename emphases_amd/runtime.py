@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -55,6 +55,12 @@ SIGNATURES = {
     'emph_logmel': (_c.c_int, [
         _ptr, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr,
         _i64, _i32, _i32, _ptr, _ptr, _i32, _ptr]),
+    'emph_frontend_mel_plan_size': (_i64, []),
+    'emph_frontend_mel_plan_fill': (_c.c_int, [
+        _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr]),
+    'emph_logmel_planned': (_c.c_int, [
+        _ptr, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr,
+        _ptr, _i64, _i32, _i32, _ptr, _ptr, _i32, _ptr]),
     'emph_frontend_peak': (_c.c_int, [
         _ptr, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr]),
     'emph_host_gather': (_c.c_int, [_ptr, _ptr, _ptr, _i32, _ptr, _i32]),
@@ -384,6 +390,31 @@ def frontend_table():
     return table
 
 
+ERANGE = -2     # EMPH_ERANGE
+
+
+def frontend_mel_plan(start, count, offset, values):
+    """The balanced mel projection of a filterbank given as row runs (host,
+    numpy; `emph_frontend_mel_plan_fill`): (plan uint32, counts int32 [5] =
+    quads, most quads of a lane, most partial sums of a lane, most lanes of a
+    row, LDS cycles of a frame's quad reads),
+    or (None, None) for a basis that does not fit - `emph_logmel_planned` then
+    runs one lane per row."""
+    lib = library()
+    start, count, offset = (np.ascontiguousarray(a, dtype=np.int32)
+                            for a in (start, count, offset))
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    plan = np.zeros(lib.emph_frontend_mel_plan_size(), dtype=np.uint32)
+    counts = np.zeros(5, dtype=np.int32)
+    status = lib.emph_frontend_mel_plan_fill(
+        start.ctypes.data, count.ctypes.data, offset.ctypes.data,
+        values.ctypes.data, values.size, plan.ctypes.data, counts.ctypes.data)
+    if status == ERANGE:
+        return None, None
+    check(status, 'emph_frontend_mel_plan_fill')
+    return plan, counts
+
+
 def linear_chain_pack(weight, natural):
     """emph_transformer_block's layout of a square Linear weight [C, C]."""
     lib = library()
@@ -442,7 +473,7 @@ class ConvModel(_c.Structure):
             'table', 'mel_start', 'mel_count', 'mel_offset', 'mel_values',
             'input_pack', 'input_bias', 'encoder_packs', 'encoder_biases',
             'decoder_packs', 'decoder_biases', 'out_weight', 'out_bias',
-            'compose')]
+            'compose', 'mel_plan')]
 
 
 class WordSumTables(_c.Structure):

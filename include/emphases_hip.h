@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 41
+#define EMPH_ABI_VERSION 42
 
 /* Segment-table fields */
 enum {
@@ -284,6 +284,39 @@ int emph_logmel(const void* audio, int32_t audio_format, const int64_t* seg,
                 int32_t mel_nnz, float* out, int64_t ld, int32_t mel_row,
                 int32_t loud_row, const float* seg_peak,
                 const float* a_weights, int32_t normalize, void* stream);
+
+/* The mel projection of emph_logmel dealt evenly over the lanes of a wave: the
+ * filterbank's non-zeros as 16-byte quads of the magnitude buffer, in row order,
+ * at most 5 per lane, every row finished by one lane from at most 4 partial
+ * sums in a fixed order (no atomics).  A third fewer multiply-adds and LDS
+ * reads per frame than one lane per row, whose short rows multiply zeros.
+ *
+ * emph_frontend_mel_plan_size   32-bit words of a plan
+ * emph_frontend_mel_plan_fill   `host_plan` from the basis (HOST pointers, the
+ *                               arrays emph_logmel takes on the device); explicit
+ *                               zeros at a run's ends are left out.  EMPH_ERANGE
+ *                               when the basis does not fit (more than 320 quads,
+ *                               or a row over more than 4 lanes): run it without
+ *                               a plan then.  `counts` (int32 [5], or NULL):
+ *                               quads, most quads of a lane, most partial sums
+ *                               of a lane, most lanes of a row, LDS cycles of
+ *                               a frame's quad reads (conflict free: 20).
+ * emph_logmel_planned           emph_logmel with `mel_plan` (device copy of the
+ *                               plan of the SAME basis; NULL: emph_logmel).  The
+ *                               mel rows differ from emph_logmel's in the order
+ *                               of a row's additions only. */
+int64_t emph_frontend_mel_plan_size(void);
+int emph_frontend_mel_plan_fill(const int32_t* mel_start, const int32_t* mel_count,
+                                const int32_t* mel_offset, const float* mel_values,
+                                int32_t mel_nnz, uint32_t* host_plan, int32_t* counts);
+int emph_logmel_planned(const void* audio, int32_t audio_format, const int64_t* seg,
+                        const int32_t* tiles, int32_t n_tiles, const float* table,
+                        const int32_t* mel_start, const int32_t* mel_count,
+                        const int32_t* mel_offset, const float* mel_values,
+                        int32_t mel_nnz, const uint32_t* mel_plan, float* out,
+                        int64_t ld, int32_t mel_row, int32_t loud_row,
+                        const float* seg_peak, const float* a_weights,
+                        int32_t normalize, void* stream);
 
 /* Per-chunk max power spectrum value, needed by librosa.amplitude_to_db's
  * top_db=80 floor, which is relative to the max over the WHOLE chunk
@@ -1068,6 +1101,7 @@ typedef struct emph_conv_model {
     const float* compose;         /* emph_conv_compose_pack of the input layer and
                                      encoder layer 0, or NULL: the conv-span path
                                      then runs them as one layer                */
+    const uint32_t* mel_plan;     /* emph_frontend_mel_plan_fill, or NULL       */
 } emph_conv_model;
 
 /* Tables of the fused per-word sum (emph_conv1d_winograd4_word_sums +
