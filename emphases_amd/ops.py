@@ -29,12 +29,15 @@ Autograd.  `conv1d_same_act` (gradients of `x`, `weight`, `bias`) and
 the way to a second backward, raises) and carry a
 `register_fake` shape rule; so is `encoder_layer` (gradients of `x` and of
 all twelve parameters; 80 channels in 2 heads, its dropouts the identity:
-see its docstring); `logmel` and `prominence_forward` stay
-non-differentiable.  The backward runs on the library's kernels
-(`emph_activation_gradient`, `emph_conv_weight_grad_any`, `emph_conv1d` on the
-flipped pack, `emph_segment_reduce_backward`, `emph_attention_backward`,
-`emph_add_layernorm_backward`), without atomics: the same inputs give the
-same bits.
+see its docstring) and `logmel` (gradient of a float `audio_packed`: the
+waveform end of the chain, so d(prominence)/d(audio) exists on the seams; no
+`register_fake` - its shape depends on the values of `cu_samples`);
+`prominence_forward` alone stays non-differentiable.  The backward runs on
+the library's kernels (`emph_activation_gradient`,
+`emph_conv_weight_grad_any`, `emph_conv1d` on the flipped pack,
+`emph_segment_reduce_backward`, `emph_attention_backward`,
+`emph_add_layernorm_backward`, `emph_logmel_backward`), without atomics: the
+same inputs give the same bits.
 
 Two paths of `conv1d_same_act`.  A weight that has never changed since the op
 first saw it (inference) takes the kernels it always took, its packs made
@@ -206,23 +209,48 @@ def _device_index(tensor):
     return tensor.device.index
 
 
-@torch.library.custom_op('emphases_amd::logmel', mutates_args=())
-def logmel(audio_packed: torch.Tensor, cu_samples: torch.Tensor) -> torch.Tensor:
-    """`mels.from_audio` (`mels.py:16-109`) of N chunks back to back: float32
-    (or int16 PCM) `[sum S_i]` -> float32 `[80, sum F_i]`, F_i = 1 + (S_i -
-    160) // 160 as in the reference (reflect padding of 432 per chunk)."""
-    index = _device_index(audio_packed)
+_logmel_plans = collections.OrderedDict()
+
+
+def _logmel_plan(cu_samples):
+    """The `batch.Plan` of N chunks back to back (a chunk = an utterance whose
+    one segment starts behind the zero padding), from a small LRU keyed by the
+    values of `cu_samples`: the forward and its backward share one."""
     samples, edges = _counts(cu_samples)
-    engine = core.get_engine(None, index, cfg.DEFAULT)
+    key = edges.tobytes()
+    with _layouts_lock:
+        found = _logmel_plans.get(key)
+        if found is not None:
+            _logmel_plans.move_to_end(key)
+            return found
     frames = [1 + (int(n) + 2 * cfg.PADDING - cfg.NUM_FFT) // cfg.HOPSIZE
               if n > cfg.PADDING else 0 for n in samples]
     if any(f <= 0 for f in frames):
         raise ValueError('a chunk needs more than 432 samples (reflect padding, mels.py:31-36)')
-    # a chunk = an utterance whose one segment starts behind the zero padding
     segments = [batch.Segment(i, 0, 0, cfg.PADDING, int(n), f,
                               np.zeros((2, 0), dtype=np.int64))
                 for i, (n, f) in enumerate(zip(samples, frames))]
-    plan = batch.Plan(segments, edges[:-1], samples)
+    found = batch.Plan(segments, edges[:-1], samples)
+    with _layouts_lock:
+        _logmel_plans[key] = found
+        while len(_logmel_plans) > PLAN_CACHE_SIZE:
+            _logmel_plans.popitem(last=False)
+    return found
+
+
+@torch.library.custom_op('emphases_amd::logmel', mutates_args=())
+def logmel(audio_packed: torch.Tensor, cu_samples: torch.Tensor) -> torch.Tensor:
+    """`mels.from_audio` (`mels.py:16-109`) of N chunks back to back: float32
+    (or int16 PCM) `[sum S_i]` -> float32 `[80, sum F_i]`, F_i = 1 + (S_i -
+    160) // 160 as in the reference (reflect padding of 432 per chunk).
+
+    Backward (once, `emph_logmel_backward`): the gradient of a float
+    `audio_packed`; nothing is saved but the inputs - the spectrum is
+    recomputed from the audio.  int16 PCM has no gradient (the output does not
+    require grad)."""
+    index = _device_index(audio_packed)
+    plan = _logmel_plan(cu_samples)
+    engine = core.get_engine(None, index, cfg.DEFAULT)
     with torch.cuda.device(index), engine.lock:
         meta = engine.upload(plan)
         packed = engine.features(audio_packed.contiguous(), plan, meta)
@@ -453,6 +481,65 @@ def _once(name):
             f'emphases_amd::{name} is differentiable once: its backward '
             'records no graph (create_graph=True / a second backward is not '
             'supported)')
+
+
+@functools.lru_cache(maxsize=8)
+def _backward_table(index):
+    """The front-end's table with the window the REFERENCE has: `torch.stft`
+    in `mels.py:39-48` is given `torch.hann_window` as torch evaluates it in
+    float32, up to 5.5e-4 relative (1.8e-7 absolute) away, at a frame's ends,
+    from the exact periodic Hann rounded to float32 that
+    `emph_frontend_table_fill` holds.  The forward keeps its table and its
+    bits; the backward differentiates the reference's function, so that the
+    gradient is the one the reference's autograd gives (after half a second of
+    digital silence the two windows' gradients are 3.6e-6 of the largest
+    element apart).  The table holds the window halved, an exact operation."""
+    engine = core.get_engine(None, index, cfg.DEFAULT)
+    table = engine.table.clone()
+    window = torch.hann_window(cfg.NUM_FFT, dtype=torch.float32)
+    table[:cfg.NUM_FFT] = (0.5 * window).to(table.device)
+    return table
+
+
+def _logmel_setup(ctx, inputs, output):
+    audio_packed, cu_samples = inputs
+    ctx.save_for_backward(audio_packed, cu_samples)
+
+
+def _logmel_backward(ctx, grad):
+    _once('logmel')
+    audio_packed, cu_samples = ctx.saved_tensors
+    if not ctx.needs_input_grad[0]:
+        return None, None
+    index = _device_index(grad)
+    plan = _logmel_plan(cu_samples)
+    engine = core.get_engine(None, index, cfg.DEFAULT)
+    lib = runtime.library()
+    with torch.cuda.device(index), engine.lock:
+        meta = engine.upload(plan)
+        tiles, size = meta[
+            ('tiles', runtime.AXIS_FRAMES, engine_module.FRONTEND_BLOCK)]
+        n_tiles = size // runtime.TILE_FIELDS
+        audio = audio_packed.detach()
+        if audio.dtype != torch.float32 or not audio.is_contiguous():
+            audio = audio.to(torch.float32).contiguous()
+        dmel = _scatter(grad, plan, plan.frame_off, plan.frames, plan.ld_frames)
+        # (samples outside every chunk - behind the last prefix sum - get 0)
+        daudio = torch.zeros_like(audio)
+        workspace = torch.empty(
+            int(lib.emph_logmel_backward_workspace(n_tiles)),
+            dtype=torch.float32, device=audio.device)
+        runtime.check(lib.emph_logmel_backward(
+            audio.data_ptr(), meta['table'][0].data_ptr(), tiles.data_ptr(),
+            n_tiles, _backward_table(index).data_ptr(), engine.mel_start.data_ptr(),
+            engine.mel_count.data_ptr(), engine.mel_offset.data_ptr(),
+            engine.mel_values.data_ptr(), engine.mel_nnz, dmel.data_ptr(),
+            plan.ld_frames, 0, workspace.data_ptr(), daudio.data_ptr(),
+            runtime.stream()), 'emph_logmel_backward')
+    return daudio.to(audio_packed.dtype).reshape(audio_packed.shape), None
+
+
+logmel.register_autograd(_logmel_backward, setup_context=_logmel_setup)
 
 
 def _conv_setup(ctx, inputs, output):

@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -61,6 +61,10 @@ SIGNATURES = {
     'emph_logmel_planned': (_c.c_int, [
         _ptr, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr,
         _ptr, _i64, _i32, _i32, _ptr, _ptr, _i32, _ptr]),
+    'emph_logmel_backward_workspace': (_i64, [_i32]),
+    'emph_logmel_backward': (_c.c_int, [
+        _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _i64,
+        _i32, _ptr, _ptr, _ptr]),
     'emph_frontend_peak': (_c.c_int, [
         _ptr, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr]),
     'emph_host_gather': (_c.c_int, [_ptr, _ptr, _ptr, _i32, _ptr, _i32]),

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 42
+#define EMPH_ABI_VERSION 43
 
 /* Segment-table fields */
 enum {
@@ -317,6 +317,37 @@ int emph_logmel_planned(const void* audio, int32_t audio_format, const int64_t* 
                         int64_t ld, int32_t mel_row, int32_t loud_row,
                         const float* seg_peak, const float* a_weights,
                         int32_t normalize, void* stream);
+
+/* Backward of the mel rows of emph_logmel (csrc/frontend_grad.hip): the gradient
+ * of the packed float32 audio from the gradient of the log-mel rows.  The
+ * forward's spectrum is recomputed from `audio`; nothing is saved by emph_logmel.
+ *
+ *   seg, tiles, n_tiles, table, mel_*   exactly what emph_logmel takes for the
+ *                same batch; the tiles of a chunk are consecutive rows of the
+ *                tile table in rising order (emph_plan_tiles)
+ *   dmel         float32 [rows][ld] in the layout of emph_logmel's `out`: rows
+ *                mel_row .. mel_row + 79 are read, the columns of real frames only
+ *   workspace    float32 [emph_logmel_backward_workspace(n_tiles)]: at most
+ *                4096 tiles x 2144 floats (33.5 MiB) whatever the batch - the
+ *                tile table is walked in runs
+ *   daudio       float32, the layout of `audio`: every sample of every chunk
+ *                that the audio backs is written, once, by one thread; samples
+ *                outside every chunk are not touched.  The chunks of the
+ *                segments must not share a sample.
+ *
+ * The mel rows as emph_logmel computes them with normalize = 0: a caller of
+ * the normalized rows scales `dmel` by 0.1.  float32 audio only.  No atomics:
+ * the same arguments give the same bits, and a chunk's gradient is the same
+ * bits alone or anywhere in a batch.  A null or misaligned pointer or
+ * n_tiles < 0 returns EMPH_EINVAL and launches nothing. */
+int64_t emph_logmel_backward_workspace(int32_t n_tiles);   /* floats */
+int emph_logmel_backward(const float* audio, const int64_t* seg, const int32_t* tiles,
+                         int32_t n_tiles, const float* table,
+                         const int32_t* mel_start, const int32_t* mel_count,
+                         const int32_t* mel_offset, const float* mel_values,
+                         int32_t mel_nnz, const float* dmel, int64_t ld,
+                         int32_t mel_row, float* workspace, float* daudio,
+                         void* stream);
 
 /* Per-chunk max power spectrum value, needed by librosa.amplitude_to_db's
  * top_db=80 floor, which is relative to the max over the WHOLE chunk
