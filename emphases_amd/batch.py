@@ -542,45 +542,53 @@ class Pieces:
     segment per word, frames = the chunk's longest word), `gather` the int64
     [n, 4] table of emph_gather_columns, and `bounds` / `word_piece` the
     emph_segment_reduce tables that pool piece p into the ORIGINAL word column
-    of its word."""
+    of its word; `piece_column` is the inverse of `word_piece` (int32 [n]: the
+    word column of piece p), which `emph_piece_pool_backward` reads.  Array
+    code over all words of the batch at once: nothing per word in Python
+    (tests/pieces_reference.py holds the per-word restatement)."""
 
     def __init__(self, parent, method):
-        segments, sources = [], []
-        for index, segment in enumerate(parent.segments):
-            starts, ends = segment.bounds[0], segment.bounds[1]
-            if not starts.size:
-                continue
-            if (starts < 0).any() or (ends > segment.frames).any() or \
-                    (ends < starts).any():
-                # the reference's slice assignment raises here too
-                raise ValueError(
-                    'word bounds outside the chunk are not supported with '
-                    "DOWNSAMPLE_LOCATION='input'")
-            longest = int((ends - starts).max())
-            if longest < 1:
+        words = np.asarray(parent.words, dtype=np.int64)
+        starts = np.asarray(parent.segment_bounds[0], dtype=np.int64)
+        ends = np.asarray(parent.segment_bounds[1], dtype=np.int64)
+        count = int(starts.size)
+        chunk = np.repeat(np.arange(len(words)), words)     # chunk of a word
+        lengths = ends - starts
+        holding = np.nonzero(words)[0]                      # chunks with words
+        first = (np.cumsum(words) - words)[holding]
+        if count:
+            outside = (starts < 0) | (ends > parent.frames[chunk]) | \
+                (lengths < 0)
+            outside = np.logical_or.reduceat(outside, first)
+            longest = np.maximum.reduceat(lengths, first)
+            refused = np.nonzero(outside | (longest < 1))[0]
+            if refused.size:
+                # (the first chunk that is refused, by its first reason)
+                if outside[refused[0]]:
+                    # the reference's slice assignment raises here too
+                    raise ValueError(
+                        'word bounds outside the chunk are not supported '
+                        "with DOWNSAMPLE_LOCATION='input'")
                 raise ValueError('no word of the chunk covers a frame')
-            for j in range(starts.size):
-                length = int(ends[j] - starts[j])
-                # center: embedding[:, length // 2]; otherwise the whole
-                # padded axis (mean divides by `longest`)
-                end = length if method == 'center' else longest
-                segments.append(Segment(
-                    0, 0, 1, 0, 0, longest,
-                    np.array([[0], [end]], dtype=np.int64)))
-                sources.append((
-                    int(parent.frame_off[index]) + int(starts[j]), length,
-                    int(parent.word_off[index]) + j))
-        self.plan = Plan(segments, [0], [0])
-        count = len(segments)
-        self.gather = np.zeros((count, 4), dtype=np.int64)
+            padded = np.repeat(longest, words[holding])
+        else:
+            padded = np.zeros(0, dtype=np.int64)
+        # center: embedding[:, length // 2]; otherwise the whole padded axis
+        # (mean divides by `longest`)
+        end = lengths if method == 'center' else padded
+        zeros = np.zeros(count, dtype=np.int64)
+        self.plan = Plan.from_columns(
+            zeros, zeros.copy(), zeros.copy(), zeros.copy(), padded,
+            np.ones(count, dtype=np.int64), np.stack([zeros, end]), [0], [0])
+        columns = parent.word_columns()
+        self.gather = np.stack(
+            [parent.frame_off[chunk] + starts, lengths, self.plan.frame_off,
+             padded], axis=1).astype(np.int64).reshape(count, 4)
         self.bounds = np.zeros((2, parent.ld_words), dtype=np.int32)
         self.word_piece = np.full(parent.ld_words, -1, dtype=np.int32)
-        for piece, (source, length, column) in enumerate(sources):
-            self.gather[piece] = (
-                source, length, self.plan.frame_off[piece],
-                self.plan.frames[piece])
-            self.bounds[:, column] = segments[piece].bounds[:, 0]
-            self.word_piece[column] = piece
+        self.bounds[1, columns] = end
+        self.word_piece[columns] = np.arange(count, dtype=np.int32)
+        self.piece_column = columns.astype(np.int32)
 
 
 def chunk_audio(audio, segment):

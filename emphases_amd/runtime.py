@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -240,6 +240,9 @@ SIGNATURES = {
     'emph_segment_reduce_backward': (_c.c_int, [
         _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _ptr,
         _i32, _i32, _ptr]),
+    'emph_piece_pool_backward': (_c.c_int, [
+        _ptr, _i64, _ptr, _ptr, _i32, _ptr, _i64, _ptr, _ptr, _i64, _i32,
+        _ptr, _i32, _i32, _ptr]),
     'emph_activation_gradient': (_c.c_int, [_ptr, _ptr, _i64, _i32, _ptr]),
     'emph_upsample': (_c.c_int, [
         _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _i32, _i32, _ptr]),

@@ -1,16 +1,97 @@
 """`python -m emphases.train` (`emphases/train/__main__.py`): the reference's
 flags, with the run's directory in place of the configuration file it is named
 after, plus where the data lies and the settings the reference reads from its
-configuration."""
+configuration - or `--config FILE`, the reference's own way of choosing an
+experiment (`config/downsample/sum-input.py` ...), read as data and never
+executed."""
 import argparse
+import ast
+import dataclasses
 from pathlib import Path
 
 import emphases_amd
 from emphases_amd.train import loop
 
 
+# torch.nn.<Name> of ACTIVATION_FUNCTION -> Config.activation
+ACTIVATION_NAMES = {
+    'ReLU': 'relu', 'GELU': 'gelu', 'SiLU': 'silu', 'LeakyReLU': 'leaky_relu'}
+# names of a configuration file that choose nothing here
+IGNORED_NAMES = ('MODULE', 'CONFIG')
+# names that are arguments of `train.train`, not fields of `Config`
+LOOP_NAMES = {'NUM_STEPS': 'num_steps',
+              'MAX_TRAINING_FRAMES': 'max_training_frames'}
+
+
+def read_config(path):
+    """The settings of a reference configuration file
+    (`emphases/config/defaults.py` names): ({Config field: value},
+    {train.train argument: value}).  The file is parsed with `ast` and never
+    executed: only upper-case assignments of literals count, and
+    `ACTIVATION_FUNCTION = torch.nn.<Name>`, which is taken by its name.
+    ValueError, naming it, for anything else."""
+    fields = {field.name for field in dataclasses.fields(emphases_amd.Config)}
+    with open(path) as file:
+        text = file.read()
+    try:
+        tree = ast.parse(text, filename=str(path))
+    except (SyntaxError, ValueError, MemoryError, RecursionError) as error:
+        raise ValueError(
+            f'{path} is not a configuration file this trainer can read: '
+            f'{error}') from None
+    overrides, loop_arguments = {}, {}
+    for node in tree.body:
+        if isinstance(node, ast.Expr) and \
+                isinstance(node.value, ast.Constant) and \
+                isinstance(node.value.value, str):
+            continue                                    # a docstring
+        if not isinstance(node, ast.Assign) or len(node.targets) != 1 or \
+                not isinstance(node.targets[0], ast.Name):
+            raise ValueError(
+                f'{path}:{node.lineno}: only assignments NAME = literal are '
+                'read from a configuration file')
+        name = node.targets[0].id
+        if name != name.upper():
+            raise ValueError(
+                f'{path}:{node.lineno}: {name} is not an upper-case setting')
+        if name in IGNORED_NAMES:
+            continue
+        if name == 'ACTIVATION_FUNCTION':
+            value = node.value
+            if not (isinstance(value, ast.Attribute) and
+                    ast.unparse(value.value) == 'torch.nn' and
+                    value.attr in ACTIVATION_NAMES):
+                raise ValueError(
+                    f'{path}:{node.lineno}: ACTIVATION_FUNCTION must be '
+                    f'torch.nn.<one of {sorted(ACTIVATION_NAMES)}>, not '
+                    f'{ast.unparse(value)}')
+            overrides['activation'] = ACTIVATION_NAMES[value.attr]
+            continue
+        try:
+            value = ast.literal_eval(node.value)
+        except (ValueError, TypeError, SyntaxError, MemoryError,
+                RecursionError):
+            raise ValueError(
+                f'{path}:{node.lineno}: the value of {name} is not a '
+                'literal') from None
+        if name in LOOP_NAMES:
+            loop_arguments[LOOP_NAMES[name]] = value
+        elif name.lower() in fields:
+            overrides[name.lower()] = value
+        else:
+            raise ValueError(
+                f'{path}:{node.lineno}: {name} is not a setting this trainer '
+                'knows')
+    return overrides, loop_arguments
+
+
 def parse_args(arguments=None):
     parser = argparse.ArgumentParser(description='Train a model')
+    parser.add_argument(
+        '--config', type=Path,
+        help='A configuration file of the reference (upper-case assignments '
+             'of literals; parsed, never executed); explicit flags override '
+             'it')
     parser.add_argument(
         '--dataset', default='libritts',
         help='The dataset to train on')
@@ -28,10 +109,10 @@ def parse_args(arguments=None):
         '--cache_dir', type=Path, default=Path('data/cache'),
         help='The dataset cache (<dataset>/mels, scores, alignment, ...)')
     parser.add_argument(
-        '--num_steps', type=int, default=loop.NUM_STEPS,
+        '--num_steps', type=int,
         help='The number of updates')
     parser.add_argument(
-        '--max_training_frames', type=int, default=loop.MAX_TRAINING_FRAMES,
+        '--max_training_frames', type=int,
         help='The frame budget of a padded training batch')
     parser.add_argument(
         '--log_interval', type=int, default=loop.LOG_INTERVAL,
@@ -65,14 +146,29 @@ def parse_args(arguments=None):
     return parser.parse_args(arguments)
 
 
-def main(arguments=None):
+def settings(arguments=None):
+    """(Config overrides, `train.train` keyword arguments) of a command line:
+    the configuration file first, explicit flags over it, the reference's
+    defaults for what neither names."""
     arguments = vars(parse_args(arguments))
-    overrides = {
-        name: arguments.pop(name)
-        for name in ('loss', 'downsample_method', 'downsample_location',
-                     'upsample_method', 'dropout')}
-    overrides = {
-        name: value for name, value in overrides.items() if value is not None}
+    path = arguments.pop('config')
+    overrides, loop_arguments = ({}, {}) if path is None else \
+        read_config(path)
+    for name in ('loss', 'downsample_method', 'downsample_location',
+                 'upsample_method', 'dropout'):
+        value = arguments.pop(name)
+        if value is not None:
+            overrides[name] = value
+    defaults = {'num_steps': loop.NUM_STEPS,
+                'max_training_frames': loop.MAX_TRAINING_FRAMES}
+    for name, default in defaults.items():
+        if arguments[name] is None:
+            arguments[name] = loop_arguments.get(name, default)
+    return overrides, arguments
+
+
+def main(arguments=None):
+    overrides, arguments = settings(arguments)
     if overrides:
         emphases_amd.configure(**overrides)
     dataset, directory = arguments.pop('dataset'), arguments.pop('directory')

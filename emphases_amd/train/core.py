@@ -34,6 +34,17 @@ halo; the 'inference' loss is the mean over all frames of the batch, the
 'loss' loss the mean over all words; the output layer, the loss and Adam
 stay float32 at either precision.
 
+`PieceTrainer` is the same step for `DOWNSAMPLE_LOCATION` 'input'
+(`model/core.py:41-87`, `core.py:552-586`): every word is cut out of the
+features and zero-padded to the longest word, every piece is encoded as a
+sequence of its own and pooled over the PADDED axis into its word's column;
+the word decoder, the output layer and the loss are `Trainer`'s.  Its
+deviation is the one above in this model's terms: every utterance is alone,
+so a word is padded to the longest word of ITS OWN utterance (what
+`batch.Pieces` lays out and what the reference's inference sees, one
+utterance per call), not to the longest word of the batch as the reference's
+padded training batch does.  `Config.dropout` is refused there.
+
 All parameters live in ONE flat device buffer in `weights.parameter_shapes`
 order (the order of `Model.parameters()`); gradients and the two Adam moments
 are buffers of the same shape.  The MFMA weight packs of the forward kernel
@@ -123,10 +134,46 @@ def check_encoder_supported(config):
         refuse('mel_feature', 'True (80..83 input features)')
 
 
+def check_pieces_supported(config):
+    """`check_supported` for `PieceTrainer`: downsample_location 'input', all
+    four reductions, no dropout."""
+    def refuse(field, supported):
+        raise NotImplementedError(
+            f'the piece training step supports {field} {supported} only, '
+            f'not {field}={getattr(config, field)!r}')
+    if config.method != 'neural':
+        refuse('method', "'neural'")
+    if config.architecture != 'convolution':
+        refuse('architecture', "'convolution'")
+    if config.downsample_location != 'input':
+        refuse('downsample_location', "'input'")
+    if config.downsample_method not in ('sum', 'average', 'max', 'center'):
+        refuse('downsample_method', "'sum', 'average', 'max' or 'center'")
+    if config.activation != 'relu':
+        refuse('activation', "'relu'")
+    if config.loss not in ('bce', 'mse'):
+        refuse('loss', "'bce' or 'mse'")
+    if config.channels != 80:
+        refuse('channels', '80')
+    if config.encoder_kernel_size != 3:
+        refuse('encoder_kernel_size', '3')
+    if config.decoder_kernel_size != 3:
+        refuse('decoder_kernel_size', '3')
+    if not 0 <= config.layers <= 16:
+        refuse('layers', '0..16')
+    if not config.mel_feature:
+        refuse('mel_feature', 'True (80..83 input features)')
+    if config.dropout is not None:
+        refuse('dropout', 'None (no mask is specified for the piece layout)')
+
+
 def _check_step(config):
-    """The check of the step that trains `config`: `Trainer`'s with a word
-    decoder, `EncoderTrainer`'s without."""
-    if config.has_decoder:
+    """The check of the step that trains `config`: `PieceTrainer`'s at
+    downsample_location 'input', `Trainer`'s with a word decoder otherwise,
+    `EncoderTrainer`'s without one."""
+    if config.downsample_location == 'input':
+        check_pieces_supported(config)
+    elif config.has_decoder:
         check_supported(config)
     else:
         check_encoder_supported(config)
@@ -1009,6 +1056,203 @@ class EncoderTrainer(_Step):
                 n_tiles, runtime.REDUCTIONS[config.downsample_method], stream),
                 'emph_segment_reduce_backward')
         self._encoder_backward(batch, buffers)
+
+
+class PieceTrainer(Trainer):
+    """`Trainer` for downsample_location 'input' (`check_pieces_supported`);
+    see the module docstring.  The same interface: `data.Loader` and
+    `train.evaluate` take it.  A batch carries the features on the frame
+    layout, as everywhere; the step gathers them into the piece layout
+    (`batch.Pieces`), runs the frame-rate layers there, and pools every piece
+    into the word column of the batch's own plan."""
+
+    _check = staticmethod(check_pieces_supported)
+
+    def metadata(self, plan):
+        """`Trainer.metadata` plus, under 'pieces', the tables of the piece
+        layout: its segment table, its frame tiles (and spans at 'bf16x3'),
+        the gather table, the piece bounds, `word_piece` and `piece_column` -
+        all in ONE copy to the device."""
+        pieces = plan.pieces(self.config.downsample_method)
+        tile = (runtime.AXIS_FRAMES, FRAME_TILE)
+        word_host, word_offsets = plan.pack_metadata(list(dict.fromkeys(
+            [(runtime.AXIS_WORDS, WORD_TILE), (runtime.AXIS_WORDS, GRAD_TILE)])))
+        piece_host, piece_offsets = pieces.plan.pack_metadata(
+            list(dict.fromkeys([tile, (runtime.AXIS_FRAMES, GRAD_TILE)])),
+            spans=self.precision == 'bf16x3')
+        extras = [('gather', pieces.gather.view(np.int32).ravel()),
+                  ('piece_bounds', pieces.bounds.ravel()),
+                  ('word_piece', pieces.word_piece),
+                  ('piece_column', pieces.piece_column)]
+        # (every part starts on a 16-byte boundary, the int64 tables included)
+        parts, cursor, extra_offsets = [word_host, piece_host], \
+            word_host.size + piece_host.size, {}
+        assert word_host.size % 4 == 0 and piece_host.size % 4 == 0
+        for name, array in extras:
+            extra_offsets[name] = (cursor, array.size)
+            padded = np.zeros(-(-max(array.size, 1) // 4) * 4, dtype=np.int32)
+            padded[:array.size] = array
+            parts.append(padded)
+            cursor += padded.size
+        host = np.concatenate(parts)
+        with torch.cuda.device(self.device):
+            device_meta = torch.from_numpy(host).to(self.device)
+        meta = {name: device_meta[start:start + size]
+                for name, (start, size) in word_offsets.items()}
+        piece_meta = {
+            name: device_meta[word_host.size + start:][:size]
+            for name, (start, size) in piece_offsets.items()}
+        piece_meta.update(
+            (name, device_meta[start:start + size])
+            for name, (start, size) in extra_offsets.items())
+        piece_meta['plan'] = pieces.plan
+        meta['pieces'] = piece_meta
+        meta['_buffer'] = device_meta
+        return meta
+
+    def _batch(self, arguments):
+        if len(arguments) == 1 and isinstance(arguments[0], Batch):
+            pieces = arguments[0].meta.get('pieces')
+            if pieces is None:
+                raise ValueError(
+                    'the batch carries no piece tables: prepare it with this '
+                    "trainer (downsample_location='input')")
+            if self._split_forward and 'conv_spans' not in pieces:
+                raise ValueError(
+                    "the batch was prepared by a trainer at precision='f32' "
+                    "and carries no span table: prepare it with this "
+                    f"trainer (precision={self.precision!r})")
+            return arguments[0]
+        return self.prepare(*arguments)
+
+    def _buffers(self, plan, piece_plan=None):
+        """The activations and gradients of a step, kept between steps (zero
+        at first, so that padding columns stay finite): the frame-rate ones on
+        the piece layout, the word-rate ones on the batch's own."""
+        if piece_plan is None:
+            piece_plan = plan.pieces(self.config.downsample_method).plan
+        frame_tiles = len(piece_plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
+        word_tiles = len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE))
+        parts = max(
+            int(self.lib.emph_conv_weight_grad_parts(n))
+            for n in (frame_tiles, word_tiles))
+        key = (piece_plan.ld_frames, plan.ld_words, parts)
+        found = self._workspace.get(key)
+        if found is None:
+            self._workspace.clear()
+            channels, layers = self.config.channels, self.config.layers
+            zeros = lambda *shape: torch.zeros(  # noqa: E731
+                shape, dtype=torch.float32, device=self.device)
+            slab = channels * 3 * self.config.num_features + channels
+            found = {
+                'piece_features': zeros(
+                    self.config.num_features, piece_plan.ld_frames),
+                'frames': zeros(layers + 1, channels, piece_plan.ld_frames),
+                'words': zeros(layers + 1, channels, plan.ld_words),
+                'frame_grad': zeros(2, channels, piece_plan.ld_frames),
+                'word_grad': zeros(2, channels, plan.ld_words),
+                'logits': zeros(plan.ld_words),
+                'dlogit': zeros(plan.ld_words),
+                'slabs': zeros(max(parts, 1) * slab)}
+            self._workspace[key] = found
+        return found
+
+    def _forward(self, batch, training=False):
+        """The forward launches of a step (`model/core.py:41-87,138`); returns
+        the step's buffers, whose 'logits' then hold the packed logits
+        [ld_words] and whose 'view' is the batch on the piece layout."""
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        pieces = meta['pieces']
+        piece_plan = pieces['plan']
+        ld_f, ld_w, ld_p = plan.ld_frames, plan.ld_words, piece_plan.ld_frames
+        buffers = self._buffers(plan, piece_plan)
+        stream = runtime.stream()
+        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
+        table, word_segment = meta['table'], meta['word_segment']
+        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
+
+        gathered = buffers['piece_features']
+        runtime.check(lib.emph_gather_columns(
+            batch.features.data_ptr(), ld_f, gathered.data_ptr(), ld_p,
+            config.num_features, pieces['gather'].data_ptr(), len(piece_plan),
+            stream), 'emph_gather_columns')
+        view = buffers['view'] = Batch(piece_plan, pieces, gathered, None)
+        h, d = buffers['frames'], buffers['words']
+        self._encoder_forward(view, h, False)
+        runtime.check(lib.emph_segment_reduce(
+            h[layers].data_ptr(), ld_p, pieces['piece_bounds'].data_ptr(),
+            d[0].data_ptr(), ld_w, channels, pieces['table'].data_ptr(),
+            pieces['word_piece'].data_ptr(), ld_w,
+            runtime.REDUCTIONS[config.downsample_method], stream),
+            'emph_segment_reduce')
+        for i, name in enumerate(decoder):
+            self._conv(self._forward_packs[name],
+                       self._parameter(f'{name}.bias'), d[i], d[i + 1], ld_w,
+                       channels, 'relu', word_tiles, WORD_TILE)
+        runtime.check(lib.emph_output_layer(
+            d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
+            self._parameter('output_layer.bias'), channels, 3,
+            table.data_ptr(), word_segment.data_ptr(), ld_w,
+            runtime.AXIS_WORDS, 0, buffers['logits'].data_ptr(), None, stream),
+            'emph_output_layer')
+        return buffers
+
+    def _forward_backward(self, batch):
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_w = plan.ld_words
+        buffers = self._forward(batch, training=True)
+        view = buffers['view']
+        ld_p = view.plan.ld_frames
+        stream = runtime.stream()
+        piece_tiles = view.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
+        word_grad_tiles = meta[('tiles', runtime.AXIS_WORDS, GRAD_TILE)]
+        word_segment = meta['word_segment']
+        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
+        h, d = buffers['frames'], buffers['words']
+        logits, dlogit = buffers['logits'], buffers['dlogit']
+
+        # ---- loss (train/core.py:315-353) and the word-rate backward
+        runtime.check(lib.emph_loss_grad(
+            logits.data_ptr(), batch.targets.data_ptr(),
+            word_segment.data_ptr(), ld_w, plan.total_words,
+            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
+            dlogit.data_ptr(), stream), 'emph_loss_grad')
+        dd, dh = buffers['word_grad'], buffers['frame_grad']
+        runtime.check(lib.emph_output_layer_backward(
+            dlogit.data_ptr(), d[layers].data_ptr(), ld_w,
+            self._parameter('output_layer.weight'), word_segment.data_ptr(),
+            channels, 3, ld_w, self._gradient('output_layer.weight'),
+            self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
+            stream), 'emph_output_layer_backward')
+        dword = self._backward_stack(
+            batch, buffers, decoder, d, dd, ld_w, word_grad_tiles, word_tiles,
+            WORD_TILE)
+        # ---- the pooled words back to the columns of their pieces
+        runtime.check(lib.emph_piece_pool_backward(
+            dword.data_ptr(), ld_w, view.meta['gather'].data_ptr(),
+            view.meta['piece_column'].data_ptr(), len(view.plan),
+            h[layers].data_ptr(), ld_p, d[0].data_ptr(), dh[0].data_ptr(),
+            ld_p, channels, piece_tiles.data_ptr(),
+            piece_tiles.numel() // runtime.TILE_FIELDS,
+            runtime.REDUCTIONS[config.downsample_method], stream),
+            'emph_piece_pool_backward')
+        self._encoder_backward(view, buffers)
+
+
+def trainer_for(config=None, **arguments):
+    """The step that trains `config` at any downsample_location: a
+    `PieceTrainer` at 'input' where `check_pieces_supported` passes,
+    `make_trainer(...)` everywhere else; the refusal that names the offending
+    field comes first, before a GPU is needed."""
+    config = config or api.active_config()
+    if config.downsample_location == 'input':
+        check_pieces_supported(config)
+        check_precision(arguments.get('precision', 'f32'))
+        return PieceTrainer(config, **arguments)
+    return make_trainer(config, **arguments)
 
 
 def make_trainer(config=None, **arguments):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 43
+#define EMPH_ABI_VERSION 44
 
 /* Segment-table fields */
 enum {
@@ -1380,6 +1380,37 @@ int emph_segment_reduce_backward(const float* dword, int64_t ldw, const int32_t*
                                  int64_t ld_dx, int32_t channels, const int64_t* seg,
                                  const int32_t* tiles, int32_t n_tiles, int32_t mode,
                                  void* stream);
+
+/* Backward of the pooling at DOWNSAMPLE_LOCATION = 'input'
+ * (model/core.py:54-71 under autograd), whose forward is emph_segment_reduce
+ * with the piece tables: piece p is a segment of its own on the piece layout's
+ * frame axis and pools into the ORIGINAL word column piece_column[p] of its
+ * word, which no segment table of the piece layout names.
+ *   pieces        int64 [n_pieces][4]  the emph_gather_columns table of the
+ *                                      pieces: (source, n, first column, L)
+ *   piece_column  int32 [n_pieces]     packed word column of piece p
+ *   tiles         the 64-wide tile table of the piece layout's frame axis
+ *                 (segment = piece, count = L)
+ *   dword, y      [channels][ldw] gradient and value of the pooled words
+ *   x             [channels][ldx] the forward's input on the piece layout
+ *                 (x and y are read for EMPH_REDUCE_MAX only; may be null
+ *                 otherwise)
+ *   dx            [channels][ld_dx] on the piece layout
+ * Per piece, with col = piece_column[p], over its L columns:
+ *   SUM      dx[c][t] = dword[c][col]
+ *   AVERAGE  dx[c][t] = dword[c][col] * (1 / L)
+ *   CENTER   dword[c][col] at column n / 2, 0 elsewhere
+ *   MAX      dword[c][col] at the first column of [0, L) whose value equals
+ *            y[c][col] (torch's tie rule for max(dim)), 0 elsewhere
+ * Every column of a piece is written by one thread; the alignment gaps
+ * between the pieces are neither read nor written; no atomics: the same
+ * inputs give the same bits.  A contract violation returns EMPH_EINVAL and
+ * launches nothing. */
+int emph_piece_pool_backward(const float* dword, int64_t ldw, const int64_t* pieces,
+                             const int32_t* piece_column, int32_t n_pieces, const float* x,
+                             int64_t ldx, const float* y, float* dx, int64_t ld_dx,
+                             int32_t channels, const int32_t* tiles, int32_t n_tiles,
+                             int32_t mode, void* stream);
 
 /* Gradient of the activation of model/layers/convolution.py:28, in place:
  * gradient[i] *= act'(.).  EMPH_ACT_RELU (the bits of

@@ -4,6 +4,7 @@
     python tools/train_bench.py --precision bf16x3 --parent <checkout of the parent commit>
     python tools/train_bench.py --dropout 0.1 --parent <checkout of the parent commit>
     python tools/train_bench.py --downsample_location inference loss --laps 3 --parent <checkout of the parent commit> --out profiles/train_step_locations.json
+    python tools/train_bench.py --downsample_location input --laps 3 --parent <checkout of the parent commit> --out profiles/train_step_input.json
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --steps 20
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --downsample_location inference --steps 20
 
@@ -40,6 +41,19 @@ batched matmul at 'loss', the frame targets of `emphases_amd.upsample`, made
 once outside the timed region and clamped, at 'inference') with autograd and
 `torch.optim.Adam` in float32, and `ours_parent` (with `--parent`) the
 'intermediate' step of the parent checkout on the same batch.
+
+With `--downsample_location input` the contenders are `ours_input`,
+`emphases_amd.train.PieceTrainer.step` (every word a zero-padded sequence of
+its own, padded to the longest word of ITS utterance), and `torch_fp32_input`:
+the same layers as torch.nn.Conv1d + ReLU over the padded pieces
+[2 250, 80, L], the pooling as a sum over the padded axis, autograd and
+`torch.optim.Adam` in float32.  torch needs one L for its batch, so its pieces
+are padded to the longest word of the BATCH, as the reference's own training
+batch is (`core.py:552-586`).  The
+record carries both column counts and the per-column times, whose ratio is
+the one that compares like with like, and the per-batch host time of the piece
+layout (plan, pieces, metadata upload); with `--parent`, also the time the
+parent checkout's own `Plan.pieces` takes on the same plan.
 
 Every utterance has the same lengths, so the padded batch of the torch model
 and the ragged batch of this package compute the same function.  A lap of one
@@ -136,6 +150,90 @@ class TorchEncoderModel(torch.nn.Module):
         return self.output_layer(frames)
 
 
+class TorchPieceModel(torch.nn.Module):
+    """`emphases.Model` at DOWNSAMPLE_LOCATION = 'input', 'sum'
+    (`model/core.py:41-87`): pieces [P, 80, L] -> word logits [B, 1, W]."""
+
+    def __init__(self, state, items, words):
+        super().__init__()
+        conv = lambda c_in, c_out: torch.nn.Conv1d(  # noqa: E731
+            c_in, c_out, kernel_size=3, padding='same')
+        stack = lambda: torch.nn.Sequential(*[  # noqa: E731
+            module for _ in range(6)
+            for module in [conv(80, 80), torch.nn.ReLU()]])
+        self.items, self.words = items, words
+        self.input_layer = conv(80, 80)
+        self.frame_encoder = stack()
+        self.word_decoder = stack()
+        self.output_layer = conv(80, 1)
+        self.load_state_dict(
+            {name: torch.from_numpy(value) for name, value in state.items()})
+
+    def forward(self, pieces, membership=None):
+        pooled = self.frame_encoder(self.input_layer(pieces)).sum(dim=2)
+        words = pooled.reshape(self.items, self.words, -1).transpose(1, 2)
+        return self.output_layer(self.word_decoder(words))
+
+
+def padded_pieces(batch):
+    """[B W, 80, L] of a batch, L the longest word of the batch."""
+    features, _, bounds, _, _ = batch
+    lengths = bounds[:, 1] - bounds[:, 0]
+    longest = int(lengths.max())
+    pieces = torch.zeros(ITEMS * WORDS, 80, longest)
+    for item in range(ITEMS):
+        for word in range(WORDS):
+            start, end = int(bounds[item, 0, word]), int(bounds[item, 1, word])
+            pieces[item * WORDS + word, :, :end - start] = \
+                features[item, :, start:end]
+    return pieces
+
+
+def piece_builder_ms(batch, repeats=20):
+    """Median ms of `Plan.pieces('sum')` of this checkout's package on the
+    batch's plan (a fresh plan each time: the pieces are cached per plan)."""
+    import time
+    from emphases_amd import core as api
+    _, frame_lengths, bounds, word_lengths, _ = batch
+    frames = [int(n) for n in frame_lengths]
+    words = [int(n) for n in word_lengths]
+    laps = []
+    for _ in range(repeats):
+        plan = api._packed_plan(frames, bounds, words)
+        start = time.perf_counter()
+        plan.pieces('sum')
+        laps.append(time.perf_counter() - start)
+    return 1e3 * float(np.median(laps))
+
+
+def host_times(trainer, batch, repeats=20):
+    """Median ms per batch of the host work of the piece layout: the plan,
+    the pieces, the metadata (one upload)."""
+    import time
+    from emphases_amd import core as api
+    _, frame_lengths, bounds, word_lengths, _ = batch
+    frames = [int(n) for n in frame_lengths]
+    words = [int(n) for n in word_lengths]
+    laps = {'plan': [], 'pieces': [], 'metadata': []}
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        start = time.perf_counter()
+        plan = api._packed_plan(frames, bounds, words)
+        planned = time.perf_counter()
+        plan.pieces('sum')
+        built = time.perf_counter()
+        trainer.metadata(plan)
+        torch.cuda.synchronize()
+        uploaded = time.perf_counter()
+        laps['plan'].append(planned - start)
+        laps['pieces'].append(built - planned)
+        laps['metadata'].append(uploaded - built)
+    record = {name: 1e3 * float(np.median(values))
+              for name, values in laps.items()}
+    record['total'] = record['plan'] + record['pieces'] + record['metadata']
+    return record
+
+
 def torch_step(model, optimizer, scaler, features, membership, targets):
     with torch.autocast('cuda', enabled=scaler is not None):
         loss = torch.nn.functional.binary_cross_entropy_with_logits(
@@ -188,6 +286,10 @@ class Parent:
     def __call__(self):
         return self.ask(0)
 
+    def piece_builder_ms(self):
+        """The parent checkout's own `Plan.pieces('sum')` on this batch."""
+        return self.ask(-1)
+
     def close(self):
         self.process.stdin.close()
         try:
@@ -209,14 +311,30 @@ def locations(arguments, batch):
     for location in arguments.downsample_location:
         config = emphases_amd.Config(downsample_location=location)
         state = train.initial_state(config, seed=0)
-        ours = train.EncoderTrainer(config, checkpoint=state, gpu=0)
+        ours = train.trainer_for(config, checkpoint=state, gpu=0)
         prepared = ours.prepare(*batch)
         keep.append((ours, prepared))
         contenders[f'ours_{location}'] = \
             lambda o=ours, p=prepared: o.step(p)
+        if location == 'input':
+            pieces = prepared.meta['pieces']['plan']
+            arguments.extra = {
+                'pieces': len(pieces), 'piece_columns': pieces.ld_frames,
+                'frame_columns': prepared.plan.ld_frames,
+                'host_ms': host_times(ours, batch)}
         if arguments.no_torch or arguments.only:
             continue
         features, frame_lengths, bounds, word_lengths, targets = batch
+        if location == 'input':
+            pieces = padded_pieces(batch).cuda()
+            arguments.extra['torch_piece_columns'] = \
+                pieces.shape[0] * pieces.shape[2]
+            model = TorchPieceModel(state, ITEMS, WORDS).cuda()
+            optimizer = torch.optim.Adam(model.parameters())
+            contenders['torch_fp32_input'] = (
+                lambda m=model, o=optimizer, f=pieces, t=targets.cuda():
+                torch_step(m, o, None, f, None, t))
+            continue
         if location == 'inference':
             targets = torch.clamp(emphases_amd.upsample(
                 targets.cuda(), bounds, word_lengths, frame_lengths, config),
@@ -241,7 +359,9 @@ def serve():
     prepared = ours.prepare(*make_batch())
     for line in sys.stdin:
         steps = int(line)
-        if steps == 0:
+        if steps < 0:
+            print(piece_builder_ms(make_batch()), flush=True)
+        elif steps == 0:
             print(float(ours.step(prepared)), flush=True)
         else:
             print(timed(lambda: ours.step(prepared), steps), flush=True)
@@ -253,6 +373,9 @@ def compare(arguments, contenders):
     if arguments.only is None and arguments.parent:
         parent = contenders['ours_parent'] = Parent(arguments.parent)
     try:
+        if parent is not None and 'host_ms' in getattr(arguments, 'extra', {}):
+            arguments.extra['host_ms']['pieces_parent'] = \
+                parent.piece_builder_ms()
         first = {}
         for name, function in contenders.items():
             first[name] = float(function())
@@ -285,6 +408,19 @@ def compare(arguments, contenders):
                    'min': float(np.min(values)), 'max': float(np.max(values))}
             for name, values in laps.items()},
         'ms_per_step_laps': laps}
+    record.update(getattr(arguments, 'extra', {}))
+    if 'torch_piece_columns' in record:
+        # torch pads to the batch's longest word and so computes more
+        # columns: the ratio that compares like with like is per column
+        median = {name: entry['median']
+                  for name, entry in record['ms_per_step'].items()}
+        record['ns_per_column'] = {
+            'ours_input': 1e6 * median['ours_input'] / record['piece_columns'],
+            'torch_fp32_input': 1e6 * median['torch_fp32_input'] /
+            record['torch_piece_columns']}
+        record['torch_over_ours_per_column'] = \
+            record['ns_per_column']['torch_fp32_input'] / \
+            record['ns_per_column']['ours_input']
     print(json.dumps(record))
     if arguments.out:
         with open(arguments.out, 'w') as file:
@@ -307,7 +443,7 @@ def main():
     parser.add_argument('--dropout', type=float, default=None)
     parser.add_argument(
         '--downsample_location', nargs='+', default=None,
-        choices=('inference', 'loss'))
+        choices=('inference', 'loss', 'input'))
     parser.add_argument('--no-torch', action='store_true')
     parser.add_argument('--serve', action='store_true', help=argparse.SUPPRESS)
     arguments = parser.parse_args()
