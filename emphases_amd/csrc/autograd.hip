@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "step.h"
 
 namespace emph {
 
@@ -100,23 +101,6 @@ __global__ __launch_bounds__(256) void segment_reduce_backward_kernel(
         }
         if (inside) dx[static_cast<int64_t>(c) * ld_dx + at] = value;
     }
-}
-
-constexpr float kLeakySlope = 0.01f;      // torch.nn.LeakyReLU default
-
-template <int ACT>
-__device__ __forceinline__ float activation_gradient(float source, float g) {
-    if (ACT == EMPH_ACT_RELU) return source > 0.f ? g : 0.f;
-    if (ACT == EMPH_ACT_LEAKY_RELU) return source > 0.f ? g : g * kLeakySlope;
-    if (ACT == EMPH_ACT_GELU) {
-        // ATen's GeluBackward, exact form: cdf + x pdf
-        const float cdf = 0.5f * (1.f + erff(source * 0.70710678118654752440f));
-        const float pdf = expf(-0.5f * source * source) * 0.39894228040143267794f;
-        return g * (cdf + source * pdf);
-    }
-    // ATen's silu_backward: sigmoid (1 + x (1 - sigmoid))
-    const float sigmoid = 1.f / (1.f + expf(-source));
-    return g * (sigmoid * (1.f + source * (1.f - sigmoid)));
 }
 
 template <int ACT>

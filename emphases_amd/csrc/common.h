@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -149,6 +150,28 @@ __device__ __forceinline__ Tile load_tile(const int32_t* tiles, int index) {
 __device__ __forceinline__ void wave_lds_fence() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
+}
+
+// The activation of model/layers/convolution.py:28: the epilogue of
+// emph_conv1d and emph_activation_dropout evaluate this one function.
+template <int ACT>
+__device__ __forceinline__ float activate(float x) {
+    if (ACT == EMPH_ACT_RELU) return fmaxf(x, 0.f);
+    if (ACT == EMPH_ACT_GELU)
+        return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f));
+    if (ACT == EMPH_ACT_SILU) return x / (1.f + expf(-x));
+    if (ACT == EMPH_ACT_LEAKY_RELU) return x > 0.f ? x : 0.01f * x;
+    return x;
+}
+
+__device__ __forceinline__ float activate(float x, int act) {
+    switch (act) {
+        case EMPH_ACT_RELU: return activate<EMPH_ACT_RELU>(x);
+        case EMPH_ACT_GELU: return activate<EMPH_ACT_GELU>(x);
+        case EMPH_ACT_SILU: return activate<EMPH_ACT_SILU>(x);
+        case EMPH_ACT_LEAKY_RELU: return activate<EMPH_ACT_LEAKY_RELU>(x);
+        default: return x;
+    }
 }
 
 }  // namespace emph

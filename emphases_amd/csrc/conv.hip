@@ -90,26 +90,6 @@ __host__ __device__ inline int round_up(int value, int multiple) {
     return (value + multiple - 1) / multiple * multiple;
 }
 
-template <int ACT>
-__device__ __forceinline__ float activate(float x) {
-    if (ACT == EMPH_ACT_RELU) return fmaxf(x, 0.f);
-    if (ACT == EMPH_ACT_GELU)
-        return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f));
-    if (ACT == EMPH_ACT_SILU) return x / (1.f + expf(-x));
-    if (ACT == EMPH_ACT_LEAKY_RELU) return x > 0.f ? x : 0.01f * x;
-    return x;
-}
-
-__device__ __forceinline__ float activate(float x, int act) {
-    switch (act) {
-        case EMPH_ACT_RELU: return activate<EMPH_ACT_RELU>(x);
-        case EMPH_ACT_GELU: return activate<EMPH_ACT_GELU>(x);
-        case EMPH_ACT_SILU: return activate<EMPH_ACT_SILU>(x);
-        case EMPH_ACT_LEAKY_RELU: return activate<EMPH_ACT_LEAKY_RELU>(x);
-        default: return x;
-    }
-}
-
 // K is walked in iterations of U k-steps (4 input rows each): the taps of one
 // row group for KS >= 3, two row groups for KS == 1.  Rows are padded with
 // zeros so that the iteration count is even (the loop is a ping-pong pair).

@@ -17,36 +17,22 @@
 #include <math.h>
 
 #include "common.h"
+#include "step.h"
 
 namespace emph {
 
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-struct Words {
-    uint32_t x, y, z, w;
-};
-
-__host__ __device__ __forceinline__ Words philox4x32_10(Words c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t first = static_cast<uint64_t>(kPhiloxM0) * c.x;
-        const uint64_t second = static_cast<uint64_t>(kPhiloxM1) * c.z;
-        c = Words{static_cast<uint32_t>(second >> 32) ^ c.y ^ k0, static_cast<uint32_t>(second),
-                  static_cast<uint32_t>(first >> 32) ^ c.w ^ k1, static_cast<uint32_t>(first)};
-        k0 += kPhiloxW0;
-        k1 += kPhiloxW1;
-    }
-    return c;
-}
+// (the generator itself is step.h's, shared with grid.hip; its constants are
+// part of the specification above)
+static_assert(kPhiloxM0 == 0xD2511F53u && kPhiloxM1 == 0xCD9E8D57u &&
+                  kPhiloxW0 == 0x9E3779B9u && kPhiloxW1 == 0xBB67AE85u,
+              "Philox-4x32 multipliers and Weyl constants");
 
 // (a select, never a product with 0: what lies in padding columns is undefined)
 __host__ __device__ __forceinline__ float4 dropout_quad(float4 v, uint64_t quad,
                                                         uint32_t stream_id, uint32_t step,
                                                         uint32_t seed_lo, uint32_t seed_hi,
                                                         uint32_t threshold, float scale) {
-    const Words r = philox4x32_10(
-        Words{static_cast<uint32_t>(quad), static_cast<uint32_t>(quad >> 32), stream_id, step},
-        seed_lo, seed_hi);
+    const Words r = dropout_words(quad, stream_id, step, seed_lo, seed_hi);
     v.x = r.x >= threshold ? v.x * scale : 0.f;
     v.y = r.y >= threshold ? v.y * scale : 0.f;
     v.z = r.z >= threshold ? v.z * scale : 0.f;
@@ -79,17 +65,6 @@ __global__ __launch_bounds__(256) void activation_dropout_backward_kernel(
     g.z = out.z > 0.f ? g.z * scale : 0.f;
     g.w = out.w > 0.f ? g.w * scale : 0.f;
     gradient[i] = g;
-}
-
-// float32(1 / (1 - p)), formed in double and rounded once.
-inline float dropout_scale(float p) {
-    return static_cast<float>(1.0 / (1.0 - static_cast<double>(p)));
-}
-
-// min(round(p 2^32), 2^32 - 1); p 2^32 is exact in double, halves go to even.
-inline uint32_t dropout_threshold(float p) {
-    const double scaled = nearbyint(static_cast<double>(p) * 4294967296.0);
-    return scaled >= 4294967295.0 ? 0xFFFFFFFFu : static_cast<uint32_t>(scaled);
 }
 
 }  // namespace emph

@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "step.h"
 
 namespace emph {
 
@@ -24,23 +25,6 @@ __global__ __launch_bounds__(256) void take_kernel(
     if (i >= count) return;
     const int32_t from = index[i];
     out[i] = from < 0 ? 0.f : src[from];
-}
-
-// Sum of `value` over the 256 threads of the block, in a fixed order (a
-// binary tree over thread indices); valid in thread 0.
-template <typename T>
-__device__ __forceinline__ T block_sum(T value, T* shared) {
-    shared[threadIdx.x] = value;
-    __syncthreads();
-#pragma unroll
-    for (int width = 128; width > 0; width >>= 1) {
-        if (static_cast<int>(threadIdx.x) < width)
-            shared[threadIdx.x] += shared[threadIdx.x + width];
-        __syncthreads();
-    }
-    const T total = shared[0];
-    __syncthreads();
-    return total;
 }
 
 // One workgroup: thread i owns columns i, i + 256, ... of the packed word
@@ -78,65 +62,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(
     if (threadIdx.x == 0) loss[0] = static_cast<float>(total / static_cast<double>(valid_words));
 }
 
-// dx of Conv1d(channels, 1, 3): a thread per (channel, column).
-__global__ __launch_bounds__(256) void output_backward_data_kernel(
-    const float* __restrict__ dlogit, const float* __restrict__ weight,
-    const int32_t* __restrict__ word_segment, int channels, int64_t columns,
-    float* __restrict__ dx, int64_t ldx) {
-    const int64_t index = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (index >= columns * channels) return;
-    const int c = static_cast<int>(index / columns);
-    const int64_t column = index - c * columns;
-    const int segment = word_segment[column];
-    float value = 0.f;
-    if (segment >= 0) {
-        // dx[c][w] = sum_j W[c][j] dlogit[w - j + 1], inside the segment
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int64_t from = column - j + 1;
-            if (from >= 0 && from < columns && word_segment[from] == segment)
-                value = fmaf(weight[c * 3 + j], dlogit[from], value);
-        }
-    }
-    dx[static_cast<int64_t>(c) * ldx + column] = value;
-}
-
-// dW and db of Conv1d(channels, 1, 3): block c < channels sums the three taps
-// of channel c, block `channels` sums the bias.
-__global__ __launch_bounds__(256) void output_backward_weight_kernel(
-    const float* __restrict__ dlogit, const float* __restrict__ x, int64_t ldx,
-    const int32_t* __restrict__ word_segment, int channels, int64_t columns,
-    float* __restrict__ dweight, float* __restrict__ dbias) {
-    __shared__ float shared[256];
-    const int c = blockIdx.x;
-    float sum[3] = {0.f, 0.f, 0.f};
-    for (int64_t column = threadIdx.x; column < columns; column += 256) {
-        const int segment = word_segment[column];
-        if (segment < 0) continue;
-        const float g = dlogit[column];
-        if (c == channels) {
-            sum[0] += g;
-            continue;
-        }
-        // dW[c][j] = sum_w dlogit[w] x[c][w + j - 1], x zero outside the segment
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int64_t from = column + j - 1;
-            if (from >= 0 && from < columns && word_segment[from] == segment)
-                sum[j] = fmaf(g, x[static_cast<int64_t>(c) * ldx + from], sum[j]);
-        }
-    }
-    if (c == channels) {
-        const float total = block_sum(sum[0], shared);
-        if (threadIdx.x == 0) dbias[0] = total;
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float total = block_sum(sum[j], shared);
-        if (threadIdx.x == 0) dweight[c * 3 + j] = total;
-    }
-}
+// (the backward of the output projection is step.h's, for any kernel size)
 
 __global__ __launch_bounds__(256) void activation_backward_kernel(
     const float4* __restrict__ y, float4* __restrict__ gradient, int64_t quads) {
@@ -254,14 +180,10 @@ int emph_output_layer_backward(const float* dlogit, const float* x, int64_t ldx,
     EMPH_REQUIRE(channels > 0 && channels <= 1024 && columns > 0 && columns <= ldx &&
                      columns <= ld_dx,
                  EMPH_EINVAL, "emph_output_layer_backward: bad shape");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    EMPH_LAUNCH(output_backward_weight_kernel, dim3(channels + 1), dim3(256), 0, s, dlogit,
-                x, ldx, word_segment, channels, columns, dweight, dbias);
-    if (int status = check_launch("emph_output_layer_backward")) return status;
-    const int64_t threads = columns * channels;
-    EMPH_LAUNCH(output_backward_data_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)),
-                dim3(256), 0, s, dlogit, weight, word_segment, channels, columns, dx, ld_dx);
-    return check_launch("emph_output_layer_backward");
+    return launch_output_backward<3>(dlogit, x, ldx, weight, word_segment, channels, columns,
+                                     dweight, dbias, dx, ld_dx,
+                                     static_cast<hipStream_t>(stream),
+                                     "emph_output_layer_backward");
 }
 
 int emph_activation_backward(const float* y, float* gradient, int64_t count,

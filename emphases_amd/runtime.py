@@ -13,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.path.join(HERE, 'libemphases_hip.so')
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 # include/emphases_hip.h
 SEG_FIELDS = 8
@@ -244,6 +244,15 @@ SIGNATURES = {
         _ptr, _i64, _ptr, _ptr, _i32, _ptr, _i64, _ptr, _ptr, _i64, _i32,
         _ptr, _i32, _i32, _ptr]),
     'emph_activation_gradient': (_c.c_int, [_ptr, _ptr, _i64, _i32, _ptr]),
+    'emph_output_layer_backward_any': (_c.c_int, [
+        _ptr, _ptr, _i64, _ptr, _ptr, _i32, _i32, _i64, _ptr, _ptr, _ptr,
+        _i64, _ptr]),
+    'emph_activation_dropout': (_c.c_int, [
+        _ptr, _ptr, _i64, _i32, _f32, _c.c_uint64, _c.c_uint32, _c.c_uint32,
+        _ptr]),
+    'emph_activation_dropout_gradient': (_c.c_int, [
+        _ptr, _ptr, _i64, _i32, _f32, _c.c_uint64, _c.c_uint32, _c.c_uint32,
+        _ptr]),
     'emph_upsample': (_c.c_int, [
         _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _i32, _i32, _ptr]),
     'emph_frame_head': (_c.c_int, [

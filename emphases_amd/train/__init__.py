@@ -8,13 +8,17 @@ differentiable operator seams for the configurations the fused steps refuse.
 fused steps, `make_trainer` and `train` refuse it).  `EncoderTrainer` is the step of the models without a word decoder
 (downsample_location 'inference' and 'loss'); `make_trainer` picks the class.
 `PieceTrainer` is the step at downsample_location 'input' (every word a padded
-sequence of its own); `trainer_for` dispatches over all four locations."""
+sequence of its own); `trainer_for` dispatches over all four locations.
+`GridTrainer` is the step of the reference's hyperparameter grid at
+'intermediate' (any activation, reduction, channel count and kernel size);
+`select_trainer` is `trainer_for` with `GridTrainer` behind it."""
 from .core import (  # noqa: F401
-    PRECISIONS, Batch, EncoderTrainer, PieceTrainer, Trainer, adam_state_dict, check_batch,
-    check_encoder_supported, check_pieces_supported, check_precision,
+    PRECISIONS, Batch, EncoderTrainer, GridTrainer, PieceTrainer, Trainer, adam_state_dict, check_batch,
+    check_encoder_supported, check_grid_supported, check_pieces_supported,
+    check_precision,
     check_supported,
     checkpoint_names, gather_tables, initial_state, layer_names, make_trainer, parameter_offsets, split_layer_names, split_pack_tables,
-    trainer_for, write_checkpoint)
+    select_trainer, trainer_for, write_checkpoint)
 from . import dropout  # noqa: F401
 from .model import (  # noqa: F401
     TorchModel, check_model_supported, initial_model_state, loss_fn)

@@ -28,7 +28,8 @@ def read_config(path):
     (`emphases/config/defaults.py` names): ({Config field: value},
     {train.train argument: value}).  The file is parsed with `ast` and never
     executed: only upper-case assignments of literals count, and
-    `ACTIVATION_FUNCTION = torch.nn.<Name>`, which is taken by its name.
+    `ACTIVATION_FUNCTION = torch.nn.<Name>`, which is taken by its name; the
+    one statement `import torch` that goes with it is skipped.
     ValueError, naming it, for anything else."""
     fields = {field.name for field in dataclasses.fields(emphases_amd.Config)}
     with open(path) as file:
@@ -45,6 +46,12 @@ def read_config(path):
                 isinstance(node.value, ast.Constant) and \
                 isinstance(node.value.value, str):
             continue                                    # a docstring
+        if isinstance(node, ast.Import) and len(node.names) == 1 and \
+                node.names[0].name == 'torch' and \
+                node.names[0].asname is None:
+            # `import torch`, the first line of the activation experiments
+            # (config/hparam-search/gelu.py ...): skipped, never executed
+            continue
         if not isinstance(node, ast.Assign) or len(node.targets) != 1 or \
                 not isinstance(node.targets[0], ast.Name):
             raise ValueError(
@@ -123,8 +130,7 @@ def parse_args(arguments=None):
     parser.add_argument(
         '--downsample_method', choices=emphases_amd.config.DOWNSAMPLE_METHODS,
         help="The word reduction: 'sum' (default), 'average', 'max' or "
-             "'center' (the last two at --downsample_location inference or "
-             'loss only)')
+             "'center'")
     parser.add_argument(
         '--downsample_location',
         choices=('intermediate', 'inference', 'loss'),
@@ -135,6 +141,23 @@ def parse_args(arguments=None):
         '--upsample_method', choices=emphases_amd.config.UPSAMPLE_METHODS,
         help="The interpolation of the targets at --downsample_location "
              "inference: 'linear' (default) or 'nearest'")
+    parser.add_argument(
+        '--activation', choices=sorted(ACTIVATION_NAMES.values()),
+        help="The activation of the conv stacks: 'relu' (default), 'gelu', "
+             "'silu' or 'leaky_relu'")
+    parser.add_argument(
+        '--channels', type=int,
+        help='The width of the conv stacks (default 80)')
+    parser.add_argument(
+        '--layers', type=int,
+        help='The layers of each conv stack (default 6)')
+    parser.add_argument(
+        '--encoder_kernel_size', type=int,
+        help='The kernel size of the frame encoder (default 3)')
+    parser.add_argument(
+        '--decoder_kernel_size', type=int,
+        help='The kernel size of the word decoder and the output layer '
+             '(default 3)')
     parser.add_argument(
         '--dropout', type=float,
         help='Dropout probability after every activation of the conv stacks '
@@ -155,7 +178,8 @@ def settings(arguments=None):
     overrides, loop_arguments = ({}, {}) if path is None else \
         read_config(path)
     for name in ('loss', 'downsample_method', 'downsample_location',
-                 'upsample_method', 'dropout'):
+                 'upsample_method', 'activation', 'channels', 'layers',
+                 'encoder_kernel_size', 'decoder_kernel_size', 'dropout'):
         value = arguments.pop(name)
         if value is not None:
             overrides[name] = value

@@ -45,6 +45,18 @@ so a word is padded to the longest word of ITS OWN utterance (what
 utterance per call), not to the longest word of the batch as the reference's
 padded training batch does.  `Config.dropout` is refused there.
 
+`GridTrainer` is the same step for the rest of the reference's hyperparameter
+grid at 'intermediate' (`config/hparam-search/*.py`,
+`config/downsample/{max,center}-intermediate.py`): any of the four
+activations and reductions, channels a multiple of 16 up to 128, kernel sizes
+1, 3, 5, 7, with or without dropout, in float32.  It runs the general kernels
+(`emph_conv1d` at the layer's own shape, `emph_conv_weight_grad_any`,
+`emph_segment_reduce_backward`, `emph_output_layer_backward_any`), keeps the
+pre-activation where the activation's derivative reads it (GELU, SiLU) and
+regenerates the dropout masks in the backward.  `select_trainer` picks a
+specialised step where one covers the configuration - which then keeps its
+bits - and `GridTrainer` where none does.
+
 All parameters live in ONE flat device buffer in `weights.parameter_shapes`
 order (the order of `Model.parameters()`); gradients and the two Adam moments
 are buffers of the same shape.  The MFMA weight packs of the forward kernel
@@ -167,14 +179,72 @@ def check_pieces_supported(config):
         refuse('dropout', 'None (no mask is specified for the piece layout)')
 
 
+GRID_CHANNELS = tuple(range(16, 129, 16))   # `TorchModel`'s rule
+GRID_KERNEL_SIZES = (1, 3, 5, 7)
+
+
+def check_grid_supported(config):
+    """`check_supported` for `GridTrainer`: the reference's hyperparameter
+    grid at downsample_location 'intermediate' - any activation, reduction,
+    channel count (a multiple of 16 up to 128) and odd kernel size up to 7."""
+    def refuse(field, supported):
+        raise NotImplementedError(
+            f'the grid training step supports {field} {supported} only, not '
+            f'{field}={getattr(config, field)!r}')
+    if config.method != 'neural':
+        refuse('method', "'neural'")
+    if config.architecture != 'convolution':
+        refuse('architecture', "'convolution'")
+    if config.downsample_location != 'intermediate':
+        refuse('downsample_location', "'intermediate'")
+    if config.downsample_method not in ('sum', 'average', 'max', 'center'):
+        refuse('downsample_method', "'sum', 'average', 'max' or 'center'")
+    if config.activation not in ('relu', 'gelu', 'silu', 'leaky_relu'):
+        refuse('activation', "'relu', 'gelu', 'silu' or 'leaky_relu'")
+    if config.loss not in ('bce', 'mse'):
+        refuse('loss', "'bce' or 'mse'")
+    if config.channels not in GRID_CHANNELS:
+        refuse('channels', 'a multiple of 16 in 16..128')
+    if config.encoder_kernel_size not in GRID_KERNEL_SIZES:
+        refuse('encoder_kernel_size', '1, 3, 5 or 7')
+    if config.decoder_kernel_size not in GRID_KERNEL_SIZES:
+        refuse('decoder_kernel_size', '1, 3, 5 or 7')
+    if not 0 <= config.layers <= 16:
+        refuse('layers', '0..16')
+    if not config.mel_feature:
+        refuse('mel_feature', 'True (80..83 input features)')
+    if config.dropout is not None and not 0. <= config.dropout < 1.:
+        refuse('dropout', 'None or a probability 0 <= p < 1')
+
+
+def check_grid_precision(precision):
+    """`check_precision` for `GridTrainer`: 'f32' only.  The split kernels of
+    'bf16x3' are Conv1d(80, 80, 3) with a ReLU flag and nothing else."""
+    if check_precision(precision) != 'f32':
+        raise NotImplementedError(
+            "the grid training step supports precision 'f32' only, not "
+            f'precision={precision!r}: the bf16 split kernels are '
+            'Conv1d(80, 80, 3) with ReLU')
+    return precision
+
+
 def _check_step(config):
     """The check of the step that trains `config`: `PieceTrainer`'s at
-    downsample_location 'input', `Trainer`'s with a word decoder otherwise,
-    `EncoderTrainer`'s without one."""
+    downsample_location 'input', `Trainer`'s with a word decoder otherwise
+    (`GridTrainer`'s where that refuses), `EncoderTrainer`'s without one."""
     if config.downsample_location == 'input':
         check_pieces_supported(config)
     elif config.has_decoder:
-        check_supported(config)
+        try:
+            check_supported(config)
+        except NotImplementedError:
+            try:
+                check_grid_supported(config)
+            except NotImplementedError:
+                pass
+            else:
+                return
+            raise
     else:
         check_encoder_supported(config)
 
@@ -1240,6 +1310,278 @@ class PieceTrainer(Trainer):
             runtime.REDUCTIONS[config.downsample_method], stream),
             'emph_piece_pool_backward')
         self._encoder_backward(view, buffers)
+
+
+class GridTrainer(_Step):
+    """`Trainer` for the reference's hyperparameter grid at
+    downsample_location 'intermediate' (`check_grid_supported`): every
+    activation, reduction, channel count and kernel size of
+    `config/hparam-search` and `config/downsample/*-intermediate.py`, at
+    precision 'f32'.  The same interface and the same deviations as `Trainer`;
+    the launches are the general kernels (`emph_conv1d` with the layer's own
+    shape, `emph_conv_weight_grad_any`, `emph_segment_reduce_backward`,
+    `emph_output_layer_backward_any`), so at the default configuration it
+    computes what `Trainer` computes but not with its bits.
+
+    ReLU and LeakyReLU differentiate off the kept output; GELU and SiLU need
+    the pre-activation, which the convolution then writes into a second set
+    of buffers ('pre_frames', 'pre_words') and `emph_activation_dropout` turns
+    into the layer's output: one pass more per layer, never a second
+    convolution.  Under dropout the backward regenerates the mask
+    (`emph_activation_dropout_gradient`)."""
+
+    _check = staticmethod(check_grid_supported)
+
+    def __init__(self, config=None, checkpoint=None, gpu=None, lr=1e-3,
+                 betas=(0.9, 0.999), eps=1e-8, seed=0, precision='f32'):
+        check_grid_precision(precision)
+        super().__init__(config, checkpoint, gpu, lr, betas, eps, seed,
+                         precision)
+        self._keeps_pre = self.config.activation in ('gelu', 'silu')
+
+    def _layer_shape(self, name):
+        """(c_in, kernel size) of conv layer `name`."""
+        _, shape = self.offsets[f'{name}.weight']
+        return shape[1], shape[2]
+
+    def _buffers(self, plan):
+        """The activations and gradients of a step for a packed layout, kept
+        between steps (zero at first, so that padding columns stay finite)."""
+        config = self.config
+        frame_tiles = len(plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
+        word_tiles = len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE))
+        channels, layers = config.channels, config.layers
+        shapes = [(config.num_features, config.encoder_kernel_size, frame_tiles)]
+        if layers:
+            shapes += [(channels, config.encoder_kernel_size, frame_tiles),
+                       (channels, config.decoder_kernel_size, word_tiles)]
+        workspace = max(
+            int(self.lib.emph_conv_weight_grad_any_workspace(
+                c_in, channels, kernel_size, tiles))
+            for c_in, kernel_size, tiles in shapes)
+        key = (plan.ld_frames, plan.ld_words, workspace)
+        found = self._workspace.get(key)
+        if found is None:
+            self._workspace.clear()
+            zeros = lambda *shape: torch.zeros(  # noqa: E731
+                shape, dtype=torch.float32, device=self.device)
+            found = {
+                'frames': zeros(layers + 1, channels, plan.ld_frames),
+                'words': zeros(layers + 1, channels, plan.ld_words),
+                'frame_grad': zeros(2, channels, plan.ld_frames),
+                'word_grad': zeros(2, channels, plan.ld_words),
+                'logits': zeros(plan.ld_words),
+                'dlogit': zeros(plan.ld_words),
+                'slabs': zeros(max(workspace, 1))}
+            if self._keeps_pre:
+                found['pre_frames'] = zeros(layers, channels, plan.ld_frames)
+                found['pre_words'] = zeros(layers, channels, plan.ld_words)
+            self._workspace[key] = found
+        return found
+
+    def _grid_conv(self, pack, bias, x, y, ld, c_in, kernel_size, activation,
+                   tiles, tile):
+        runtime.check(self.lib.emph_conv1d(
+            x.data_ptr(), ld, y.data_ptr(), ld,
+            self.packs.data_ptr() + 4 * pack[0], bias, c_in,
+            self.config.channels, kernel_size,
+            runtime.ACTIVATIONS[activation], tiles.data_ptr(),
+            tiles.numel() // runtime.TILE_FIELDS, tile, 0, runtime.stream()),
+            'emph_conv1d')
+
+    def _forward_stack(self, names, outputs, pre, ld, tiles, tile, training):
+        """A conv stack (`model/layers/convolution.py:22-37`): outputs[i + 1]
+        = dropout(act(conv(outputs[i]))), every output kept, and the
+        pre-activation too where the activation's derivative reads it."""
+        activation = self.config.activation
+        drop = training and self.dropout > 0.
+        for i, name in enumerate(names):
+            c_in, kernel_size = self._layer_shape(name)
+            bias = self._parameter(f'{name}.bias')
+            pack = self._forward_packs[name]
+            if training and self._keeps_pre:
+                self._grid_conv(pack, bias, outputs[i], pre[i], ld, c_in,
+                                kernel_size, None, tiles, tile)
+                runtime.check(self.lib.emph_activation_dropout(
+                    pre[i].data_ptr(), outputs[i + 1].data_ptr(),
+                    pre[i].numel(), runtime.ACTIVATIONS[activation],
+                    self.dropout if drop else 0., self.seed & (1 << 64) - 1,
+                    dropout_module.stream_of(self.config, name), self.steps,
+                    runtime.stream()), 'emph_activation_dropout')
+                continue
+            self._grid_conv(pack, bias, outputs[i], outputs[i + 1], ld, c_in,
+                            kernel_size, activation, tiles, tile)
+            if drop:
+                self._dropout(name, outputs[i + 1])
+
+    def _forward(self, batch, training=False):
+        """The forward launches of a step; returns the step's buffers, whose
+        'logits' then hold the packed logits [ld_words].  `training`: the
+        train-mode forward, which keeps what the backward reads and applies
+        the dropout masks of the step; without it the eval model, whose GELU
+        and SiLU run in the convolution's epilogue (the same function, the
+        same bits)."""
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_f, ld_w = plan.ld_frames, plan.ld_words
+        buffers = self._buffers(plan)
+        stream = runtime.stream()
+        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
+        table, word_segment = meta['table'], meta['word_segment']
+        h, d = buffers['frames'], buffers['words']
+
+        self._grid_conv(
+            self._forward_packs['input_layer'],
+            self._parameter('input_layer.bias'), batch.features, h[0], ld_f,
+            config.num_features, config.encoder_kernel_size, None,
+            frame_tiles, FRAME_TILE)
+        self._forward_stack(
+            [f'frame_encoder.{2 * i}' for i in range(layers)], h,
+            buffers.get('pre_frames'), ld_f, frame_tiles, FRAME_TILE, training)
+        runtime.check(lib.emph_segment_reduce(
+            h[layers].data_ptr(), ld_f, meta['bounds'].data_ptr(),
+            d[0].data_ptr(), ld_w, channels, table.data_ptr(),
+            word_segment.data_ptr(), ld_w,
+            runtime.REDUCTIONS[config.downsample_method], stream),
+            'emph_segment_reduce')
+        self._forward_stack(
+            [f'word_decoder.{2 * i}' for i in range(layers)], d,
+            buffers.get('pre_words'), ld_w, word_tiles, WORD_TILE, training)
+        runtime.check(lib.emph_output_layer(
+            d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
+            self._parameter('output_layer.bias'), channels,
+            config.decoder_kernel_size, table.data_ptr(),
+            word_segment.data_ptr(), ld_w, runtime.AXIS_WORDS, 0,
+            buffers['logits'].data_ptr(), None, stream), 'emph_output_layer')
+        return buffers
+
+    def _grid_weight_grad(self, dy, x, ld, name, tiles, buffers):
+        c_in, kernel_size = self._layer_shape(name)
+        runtime.check(self.lib.emph_conv_weight_grad_any(
+            dy.data_ptr(), ld, x.data_ptr(), ld, c_in, self.config.channels,
+            kernel_size, tiles.data_ptr(),
+            tiles.numel() // runtime.TILE_FIELDS, GRAD_TILE,
+            buffers['slabs'].data_ptr(), self._gradient(f'{name}.weight'),
+            self._gradient(f'{name}.bias'), runtime.stream()),
+            'emph_conv_weight_grad_any')
+
+    def _grid_backward_stack(self, buffers, names, outputs, pre, gradient, ld,
+                             grad_tiles, tiles, tile):
+        """Backward of a conv stack, from the gradient of the last output
+        (gradient[0]) down to the gradient of outputs[0]; returns the buffer
+        that holds it."""
+        lib, config, stream = self.lib, self.config, runtime.stream()
+        activation = runtime.ACTIVATIONS[config.activation]
+        current = 0
+        for i in range(len(names) - 1, -1, -1):
+            name = names[i]
+            dy = gradient[current]
+            source = pre[i] if self._keeps_pre else outputs[i + 1]
+            if self.dropout > 0.:
+                runtime.check(lib.emph_activation_dropout_gradient(
+                    source.data_ptr(), dy.data_ptr(), dy.numel(), activation,
+                    self.dropout, self.seed & (1 << 64) - 1,
+                    dropout_module.stream_of(config, name), self.steps,
+                    stream), 'emph_activation_dropout_gradient')
+            else:
+                runtime.check(lib.emph_activation_gradient(
+                    source.data_ptr(), dy.data_ptr(), dy.numel(), activation,
+                    stream), 'emph_activation_gradient')
+            self._grid_weight_grad(dy, outputs[i], ld, name, grad_tiles,
+                                   buffers)
+            _, kernel_size = self._layer_shape(name)
+            self._grid_conv(self._backward_packs[name], None, dy,
+                            gradient[1 - current], ld, config.channels,
+                            kernel_size, None, tiles, tile)
+            current = 1 - current
+        return gradient[current]
+
+    def _forward_backward(self, batch):
+        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
+        channels, layers = config.channels, config.layers
+        ld_f, ld_w = plan.ld_frames, plan.ld_words
+        buffers = self._forward(batch, training=True)
+        stream = runtime.stream()
+        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
+        word_grad_tiles = meta[('tiles', runtime.AXIS_WORDS, GRAD_TILE)]
+        table, bounds = meta['table'], meta['bounds']
+        word_segment = meta['word_segment']
+        h, d = buffers['frames'], buffers['words']
+        dh, dd = buffers['frame_grad'], buffers['word_grad']
+        logits, dlogit = buffers['logits'], buffers['dlogit']
+
+        # ---- loss (train/core.py:315-353) and the word-rate backward
+        runtime.check(lib.emph_loss_grad(
+            logits.data_ptr(), batch.targets.data_ptr(),
+            word_segment.data_ptr(), ld_w, plan.total_words,
+            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
+            dlogit.data_ptr(), stream), 'emph_loss_grad')
+        runtime.check(lib.emph_output_layer_backward_any(
+            dlogit.data_ptr(), d[layers].data_ptr(), ld_w,
+            self._parameter('output_layer.weight'), word_segment.data_ptr(),
+            channels, config.decoder_kernel_size, ld_w,
+            self._gradient('output_layer.weight'),
+            self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
+            stream), 'emph_output_layer_backward_any')
+        dword = self._grid_backward_stack(
+            buffers, [f'word_decoder.{2 * i}' for i in range(layers)], d,
+            buffers.get('pre_words'), dd, ld_w, word_grad_tiles, word_tiles,
+            WORD_TILE)
+        # ---- the reduce (max reads the encoder's output and the pooled
+        # words, both kept), the frame encoder and the input layer
+        runtime.check(lib.emph_segment_reduce_backward(
+            dword.data_ptr(), ld_w, bounds.data_ptr(), h[layers].data_ptr(),
+            ld_f, d[0].data_ptr(), dh[0].data_ptr(), ld_f, channels,
+            table.data_ptr(), frame_tiles.data_ptr(),
+            frame_tiles.numel() // runtime.TILE_FIELDS,
+            runtime.REDUCTIONS[config.downsample_method], stream),
+            'emph_segment_reduce_backward')
+        dinput = self._grid_backward_stack(
+            buffers, [f'frame_encoder.{2 * i}' for i in range(layers)], h,
+            buffers.get('pre_frames'), dh, ld_f, frame_tiles, frame_tiles,
+            FRAME_TILE)
+        self._grid_weight_grad(dinput, batch.features, ld_f, 'input_layer',
+                               frame_tiles, buffers)
+
+
+def _select(config, precision):
+    """The class of the step that trains `config`, every check made and
+    nothing constructed: the specialised step of the configuration's location
+    (what `trainer_for` builds) first, `GridTrainer` where that refuses and
+    `check_grid_supported` passes, otherwise the specialised step's refusal."""
+    location = config.downsample_location
+    if location == 'input':
+        check, name = check_pieces_supported, 'PieceTrainer'
+    elif location in ('inference', 'loss'):
+        check, name = check_encoder_supported, 'EncoderTrainer'
+    else:
+        check, name = check_supported, 'Trainer'
+    try:
+        check(config)
+    except NotImplementedError:
+        try:
+            check_grid_supported(config)
+        except NotImplementedError:
+            pass
+        else:
+            check_grid_precision(precision)
+            return globals()['GridTrainer']
+        raise
+    check_precision(precision)
+    return globals()[name]
+
+
+def select_trainer(config=None, **arguments):
+    """The fused step that trains `config`: what `trainer_for` returns where
+    a specialised step covers it (so such a configuration keeps that step and
+    its bits), a `GridTrainer` where none does and `check_grid_supported`
+    passes; otherwise the specialised step's refusal.  Every check comes
+    before anything is constructed or a GPU is needed."""
+    config = config or api.active_config()
+    return _select(config, arguments.get('precision', 'f32'))(
+        config, **arguments)
 
 
 def trainer_for(config=None, **arguments):

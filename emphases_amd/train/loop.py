@@ -1,7 +1,8 @@
 """The training loop of the convolution model (`emphases/train/core.py:13-307`):
 resume, train, validate, save - around `Trainer.step` (`EncoderTrainer.step`
-at downsample_location 'inference' and 'loss', `PieceTrainer.step` at 'input':
-`trainer_for`), fed by the resident
+at downsample_location 'inference' and 'loss', `PieceTrainer.step` at 'input',
+`GridTrainer.step` for the rest of the hyperparameter grid at 'intermediate':
+`select_trainer`), fed by the resident
 loader of `emphases_amd.data`.
 
 Deviations from the reference, besides those of the step (`train/core.py`
@@ -108,13 +109,7 @@ def train(dataset, directory, gpu=None, *, partition_dir,
     Returns the final checkpoint's path."""
     from .. import data
     config = config or api.active_config()
-    if config.downsample_location in ('inference', 'loss'):
-        core.check_encoder_supported(config)        # before any file is read
-    elif config.downsample_location == 'input':
-        core.check_pieces_supported(config)
-    else:
-        core.check_supported(config)
-    core.check_precision(precision)
+    core._select(config, precision)                 # before any file is read
     directory = os.fspath(directory)
     os.makedirs(directory, exist_ok=True)
 
@@ -133,11 +128,11 @@ def train(dataset, directory, gpu=None, *, partition_dir,
         score, best = float(state['score']), float(state['best'])
         # (the seed keys the dropout masks; the step count, which the
         # optimizer state restores, continues their stream)
-        trainer = core.trainer_for(
+        trainer = core.select_trainer(
             config, checkpoint=state, gpu=gpu, seed=seed,
             precision=precision)
     else:
-        trainer = core.trainer_for(
+        trainer = core.select_trainer(
             config, gpu=gpu, seed=seed, precision=precision)
     train_loader = loader('train', trainer, max_training_frames)
     # (the reference's validation sampler is `Sampler(dataset)`: the default

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define EMPH_ABI_VERSION 44
+#define EMPH_ABI_VERSION 45
 
 /* Segment-table fields */
 enum {
@@ -1422,6 +1422,51 @@ int emph_piece_pool_backward(const float* dword, int64_t ldw, const int64_t* pie
  * aligned, as emph_activation_backward. */
 int emph_activation_gradient(const float* source, float* gradient, int64_t count,
                              int32_t activation, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* The hyperparameter grid's fused step (csrc/grid.hip)                      */
+/* ------------------------------------------------------------------------ */
+
+/* emph_output_layer_backward for kernel_size 1, 3, 5 or 7 (anything else:
+ * EMPH_ERANGE), channels 1..1024, with p = (kernel_size - 1) / 2:
+ *   dweight[c][j] = sum_w dlogit[w] x[c][w + j - p]    dbias[0] = sum_w dlogit[w]
+ *   dx[c][w] = sum_j weight[c][j] dlogit[w - j + p]    (0 on padding columns)
+ * every sum inside the segment of w.  Columns of x outside the segment are
+ * selected away, never multiplied: a NaN there reaches no result.  Every
+ * element of dweight [channels][kernel_size], dbias [1] and dx
+ * [channels][columns] is written.  The work split is
+ * emph_output_layer_backward's (a block per channel, a strided sum over the
+ * columns, a fixed tree): at kernel_size 3 it gives that entry's bits, and
+ * the same arguments give the same bits on every launch. */
+int emph_output_layer_backward_any(const float* dlogit, const float* x, int64_t ldx,
+                                   const float* weight, const int32_t* word_segment,
+                                   int32_t channels, int32_t kernel_size, int64_t columns,
+                                   float* dweight, float* dbias, float* dx, int64_t ld_dx,
+                                   void* stream);
+
+/* Activation + dropout on a kept pre-activation, out of place (y == z is
+ * allowed): y[i] = kept(i) ? act(z[i]) * scale : +0.f.  `act` is the function
+ * of emph_conv1d's epilogue (any EMPH_ACT_*), `kept` and `scale` those of
+ * emph_dropout with origin 0; a select, so a dropped NaN becomes 0.  p = 0
+ * gives act(z) (EMPH_ACT_NONE: a copy) without drawing anything.
+ *
+ * emph_activation_dropout_gradient, in place: gradient[i] = kept(i) ?
+ * act'(.) * (gradient[i] * scale) : 0, the mask REGENERATED from the same
+ * counters.  `source` and act' are emph_activation_gradient's: the saved
+ * output for EMPH_ACT_RELU and EMPH_ACT_LEAKY_RELU (after dropout it has the
+ * sign of the pre-activation wherever the element was kept), the
+ * pre-activation for EMPH_ACT_GELU and EMPH_ACT_SILU.  With p = 0 it gives the
+ * bits of emph_activation_gradient, for EMPH_ACT_RELU those of
+ * emph_activation_dropout_backward.
+ *
+ * Both: count a multiple of 4 below 2^39, pointers 16-byte aligned,
+ * 0 <= p < 1; anything else returns EMPH_EINVAL and launches nothing. */
+int emph_activation_dropout(const float* z, float* y, int64_t count, int32_t activation,
+                            float p, uint64_t seed, uint32_t stream_id, uint32_t step,
+                            void* stream);
+int emph_activation_dropout_gradient(const float* source, float* gradient, int64_t count,
+                                     int32_t activation, float p, uint64_t seed,
+                                     uint32_t stream_id, uint32_t step, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Frame-rate head: DOWNSAMPLE_LOCATION 'inference' in train mode            */

@@ -5,6 +5,8 @@
     python tools/train_bench.py --dropout 0.1 --parent <checkout of the parent commit>
     python tools/train_bench.py --downsample_location inference loss --laps 3 --parent <checkout of the parent commit> --out profiles/train_step_locations.json
     python tools/train_bench.py --downsample_location input --laps 3 --parent <checkout of the parent commit> --out profiles/train_step_input.json
+    python tools/train_bench.py --activation gelu --laps 3 --parent <checkout of the parent commit> --out profiles/train_step_grid.json
+    python tools/train_bench.py --channels 64 --encoder_kernel_size 5 --decoder_kernel_size 1 --laps 3 --parent <checkout> --out profiles/train_step_grid.json
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --steps 20
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/train_bench.py --only ours --downsample_location inference --steps 20
 
@@ -54,6 +56,22 @@ record carries both column counts and the per-column times, whose ratio is
 the one that compares like with like, and the per-batch host time of the piece
 layout (plan, pieces, metadata upload); with `--parent`, also the time the
 parent checkout's own `Plan.pieces` takes on the same plan.
+
+With any of `--activation`, `--channels`, `--encoder_kernel_size`,
+`--decoder_kernel_size` and `--downsample_method` the contenders are those of
+the reference's hyperparameter grid at 'intermediate' under that
+configuration: `ours_grid`, `emphases_amd.train.GridTrainer.step`;
+`torch_fp32_grid`, the same model as torch.nn.Conv1d + activation modules
+built from the same settings (the word reduction as the batched matmul for
+'sum' and 'average', `torch.segment_reduce` for 'max', a gather of the middle
+frame for 'center'), autograd and `torch.optim.Adam` in float32; `seams`,
+`emphases_amd.train.TorchModel` + `torch.optim.Adam` on the differentiable
+operator seams; and with `--parent`, `seams_parent`, the same on the package
+of the parent checkout, and `ours_parent`, that checkout's `Trainer.step` at
+the default configuration.  `--out` then holds one record per configuration:
+a run adds its own to the file, under the name made of its settings, and
+the record carries the launch timer's times of the three kernels of
+csrc/grid.hip on the batch's buffers with the bytes they move.
 
 Every utterance has the same lengths, so the padded batch of the torch model
 and the ragged batch of this package compute the same function.  A lap of one
@@ -175,6 +193,180 @@ class TorchPieceModel(torch.nn.Module):
         return self.output_layer(self.word_decoder(words))
 
 
+ACTIVATION_MODULES = {
+    'relu': torch.nn.ReLU, 'gelu': torch.nn.GELU, 'silu': torch.nn.SiLU,
+    'leaky_relu': torch.nn.LeakyReLU}
+GRID_FLAGS = ('activation', 'channels', 'encoder_kernel_size',
+              'decoder_kernel_size', 'downsample_method')
+COPY_RATE = 6.29e12      # bytes/s of a device copy on this part (README)
+
+
+class TorchGridModel(torch.nn.Module):
+    """`emphases.Model` at 'intermediate' under any configuration of the
+    hyperparameter grid (`model/core.py`, `model/layers/convolution.py`)."""
+
+    def __init__(self, config, state):
+        super().__init__()
+        conv = lambda c_in, c_out, k: torch.nn.Conv1d(  # noqa: E731
+            c_in, c_out, kernel_size=k, padding='same')
+        channels = config.channels
+        stack = lambda k: torch.nn.Sequential(*[  # noqa: E731
+            module for _ in range(config.layers)
+            for module in [conv(channels, channels, k),
+                           ACTIVATION_MODULES[config.activation]()]])
+        self.method = config.downsample_method
+        self.input_layer = conv(
+            config.num_features, channels, config.encoder_kernel_size)
+        self.frame_encoder = stack(config.encoder_kernel_size)
+        self.word_decoder = stack(config.decoder_kernel_size)
+        self.output_layer = conv(channels, 1, config.decoder_kernel_size)
+        self.load_state_dict(
+            {name: torch.from_numpy(value) for name, value in state.items()})
+
+    def forward(self, features, membership):
+        """membership: the 0/1 matrix [B, T, W] for 'sum'; (matrix, word
+        lengths [B, 1, W]) for 'average'; the word lengths [B W] of words
+        that tile every utterance for 'max'; the middle frames [B, 1, W] for
+        'center'."""
+        frames = self.frame_encoder(self.input_layer(features))
+        if self.method == 'sum':
+            words = torch.bmm(frames, membership)
+        elif self.method == 'average':
+            words = torch.bmm(frames, membership[0]) / membership[1]
+        elif self.method == 'max':
+            items, channels, count = frames.shape
+            flat = frames.permute(0, 2, 1).reshape(items * count, channels)
+            words = torch.segment_reduce(
+                flat, 'max', lengths=membership, axis=0).reshape(
+                    items, -1, channels).permute(0, 2, 1)
+        else:
+            words = torch.gather(
+                frames, 2, membership.expand(-1, frames.shape[1], -1))
+        return self.output_layer(self.word_decoder(words))
+
+
+def grid_membership(method, bounds):
+    """What `TorchGridModel.forward` takes for `method`, on the device."""
+    bounds = bounds.cuda()
+    lengths = (bounds[:, 1] - bounds[:, 0])
+    if method == 'max':
+        assert int(lengths.sum()) == ITEMS * FRAMES     # the words tile
+        return lengths.reshape(-1)
+    if method == 'center':
+        return (bounds[:, 0] + lengths // 2)[:, None, :]
+    frame = torch.arange(FRAMES, device='cuda')[None, :, None]
+    matrix = ((frame >= bounds[:, 0, None, :]) &
+              (frame < bounds[:, 1, None, :])).float()
+    if method == 'sum':
+        return matrix
+    return matrix, lengths[:, None, :].float()
+
+
+def seams_step(config, state, batch):
+    """One step of `train.TorchModel` + Adam on the batch back to back."""
+    features, _, bounds, _, targets = batch
+    model = train.TorchModel(config, checkpoint=state).cuda()
+    optimizer = torch.optim.Adam(model.parameters())
+    flat = (features.permute(1, 0, 2).reshape(
+                features.shape[1], ITEMS * FRAMES).cuda(),
+            torch.arange(ITEMS + 1) * FRAMES,
+            bounds.permute(1, 0, 2).reshape(2, ITEMS * WORDS),
+            torch.arange(ITEMS + 1) * WORDS)
+    flat_targets = targets.reshape(ITEMS * WORDS).cuda()
+
+    def step():
+        optimizer.zero_grad(set_to_none=True)
+        loss = train.loss_fn(model(*flat), flat_targets, config.loss)
+        loss.backward()
+        optimizer.step()
+        return loss.detach()
+    return step
+
+
+def grid_kernels(trainer, prepared, repeats=9):
+    """Median microseconds of the three kernels of csrc/grid.hip alone on the
+    step's own buffers (the launch timer: the kernel's begin -> end), and
+    the bytes each reads and writes over `COPY_RATE`."""
+    from emphases_amd import runtime
+    lib, config = runtime.library(), trainer.config
+    buffers = trainer._buffers(prepared.plan)
+    frames, grads = buffers['frames'][1], buffers['frame_grad'][0].clone()
+    source = buffers.get('pre_frames', buffers['frames'])[0]
+    words, meta = buffers['words'], prepared.meta
+    ld_w, channels = prepared.plan.ld_words, config.channels
+    activation = runtime.ACTIVATIONS[config.activation]
+    scratch = torch.zeros_like(frames)
+    dweight = torch.zeros(channels * config.decoder_kernel_size + 1,
+                          device=frames.device)
+    launches = {
+        'emph_activation_dropout': lambda p: lib.emph_activation_dropout(
+            source.data_ptr(), scratch.data_ptr(), source.numel(), activation,
+            p, 1, 1, 0, runtime.stream()),
+        'emph_activation_dropout_gradient':
+            lambda p: lib.emph_activation_dropout_gradient(
+                source.data_ptr(), grads.data_ptr(), grads.numel(),
+                activation, p, 1, 1, 0, runtime.stream()),
+        'emph_output_layer_backward_any':
+            lambda p: lib.emph_output_layer_backward_any(
+                buffers['dlogit'].data_ptr(), words[-1].data_ptr(), ld_w,
+                trainer._parameter('output_layer.weight'),
+                meta['word_segment'].data_ptr(), channels,
+                config.decoder_kernel_size, ld_w, dweight.data_ptr(),
+                dweight[-1:].data_ptr(), buffers['word_grad'][0].data_ptr(),
+                ld_w, runtime.stream())}
+    elements = source.numel()
+    moved = {'emph_activation_dropout': 8 * elements,
+             'emph_activation_dropout_gradient': 12 * elements,
+             'emph_output_layer_backward_any':
+                 4 * (2 * channels * ld_w + 3 * ld_w)}
+    record = {'elements': elements, 'copy_rate': COPY_RATE}
+    for name, launch in launches.items():
+        for p in (0., 0.1):
+            if name == 'emph_output_layer_backward_any' and p:
+                continue
+            times = []
+            for lap in range(repeats + 1):
+                with runtime.LaunchTimer() as timer:
+                    runtime.check(launch(p), name)
+                if lap:                             # (the first lap warms up)
+                    times.append(float(sum(timer.microseconds)))
+            median = float(np.median(times))
+            record[name + ('' if not p else f'_p{p}')] = {
+                'us_median': median, 'us_min': min(times), 'us_max': max(times),
+                'bytes': moved[name],
+                'rate_over_copy': moved[name] / (median * 1e-6) / COPY_RATE}
+    return record
+
+
+def grid(arguments, batch, settings):
+    """The contenders of a configuration of the hyperparameter grid."""
+    config = emphases_amd.Config(**settings)
+    state = train.initial_state(config, seed=0)
+    ours = train.GridTrainer(config, checkpoint=state, gpu=0)
+    prepared = ours.prepare(*batch)
+    arguments.keep = (ours, prepared)
+    contenders = {'ours_grid': lambda: ours.step(prepared)}
+    arguments.extra = {'config': settings}
+    if not arguments.only:
+        arguments.extra['kernels'] = grid_kernels(ours, prepared)
+    if arguments.no_torch or arguments.only:
+        return contenders
+    features, _, bounds, _, targets = batch
+    model = TorchGridModel(config, state).cuda()
+    optimizer = torch.optim.Adam(model.parameters())
+    membership = grid_membership(config.downsample_method, bounds)
+    contenders['torch_fp32_grid'] = (
+        lambda m=model, o=optimizer, f=features.cuda(), t=targets.cuda():
+        torch_step(m, o, None, f, membership, t))
+    contenders['seams'] = seams_step(config, state, batch)
+    if arguments.parent:
+        flags = [item for name, value in settings.items()
+                 for item in (f'--{name}', str(value))]
+        contenders['seams_parent'] = Parent(
+            arguments.parent, ['seams'] + flags)
+    return contenders
+
+
 def padded_pieces(batch):
     """[B W, 80, L] of a batch, L the longest word of the batch."""
     features, _, bounds, _, _ = batch
@@ -265,11 +457,12 @@ class Parent:
     (`--serve` of that checkout's copy of this batch and trainer, driven by
     this file): a lap is a line to its stdin, the answer its ms per step."""
 
-    def __init__(self, directory):
+    def __init__(self, directory, serve=()):
         import subprocess
         directory = os.path.abspath(directory)
         self.process = subprocess.Popen(
-            [sys.executable, os.path.abspath(__file__), '--serve'],
+            [sys.executable, os.path.abspath(__file__), '--serve',
+             *serve],
             cwd=directory, env=dict(os.environ, EMPHASES_BENCH_ROOT=directory),
             stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
 
@@ -351,20 +544,32 @@ def locations(arguments, batch):
     return contenders
 
 
-def serve():
-    """The child of `Parent`: 0 -> one step, its loss; n -> a timed lap."""
+def serve(what, settings):
+    """The child of `Parent`: 0 -> one step, its loss; n -> a timed lap.
+    what: 'trainer', `Trainer.step` at the default configuration, or 'seams',
+    `TorchModel` + Adam under `settings`."""
     torch.cuda.set_device(0)
-    state = train.initial_state(emphases_amd.DEFAULT, seed=0)
-    ours = train.Trainer(checkpoint=state, gpu=0)
-    prepared = ours.prepare(*make_batch())
+    if what == 'seams':
+        config = emphases_amd.Config(**settings)
+        # (the state as arrays: a checkout older than the grid step builds
+        # only the default configuration's state itself)
+        model = train.TorchModel(config, seed=0)
+        state = {name: value.detach().numpy()
+                 for name, value in model.state_dict().items()}
+        step = seams_step(config, state, make_batch())
+    else:
+        state = train.initial_state(emphases_amd.DEFAULT, seed=0)
+        ours = train.Trainer(checkpoint=state, gpu=0)
+        prepared = ours.prepare(*make_batch())
+        step = lambda: ours.step(prepared)  # noqa: E731
     for line in sys.stdin:
         steps = int(line)
         if steps < 0:
             print(piece_builder_ms(make_batch()), flush=True)
         elif steps == 0:
-            print(float(ours.step(prepared)), flush=True)
+            print(float(step()), flush=True)
         else:
-            print(timed(lambda: ours.step(prepared), steps), flush=True)
+            print(timed(step, steps), flush=True)
 
 
 def compare(arguments, contenders):
@@ -372,6 +577,7 @@ def compare(arguments, contenders):
     parent = None
     if arguments.only is None and arguments.parent:
         parent = contenders['ours_parent'] = Parent(arguments.parent)
+    children = [c for c in contenders.values() if isinstance(c, Parent)]
     try:
         if parent is not None and 'host_ms' in getattr(arguments, 'extra', {}):
             arguments.extra['host_ms']['pieces_parent'] = \
@@ -388,7 +594,7 @@ def compare(arguments, contenders):
             steps[name] = arguments.steps or max(
                 5, int(arguments.seconds * 1e3 / probe))
         if arguments.only:
-            name = f'ours_{arguments.downsample_location[0]}'
+            name = next(iter(contenders))
             timed(contenders[name], steps[name])
             print(json.dumps({f'{name}_steps': steps[name]}))
             return
@@ -397,8 +603,8 @@ def compare(arguments, contenders):
             for name, function in contenders.items():
                 laps[name].append(run_lap(function, steps[name]))
     finally:
-        if parent is not None:
-            parent.close()
+        for child in children:
+            child.close()
     record = {
         'batch': {'utterances': ITEMS, 'frames': FRAMES, 'words': WORDS},
         'device': torch.cuda.get_device_name(0),
@@ -421,6 +627,21 @@ def compare(arguments, contenders):
         record['torch_over_ours_per_column'] = \
             record['ns_per_column']['torch_fp32_input'] / \
             record['ns_per_column']['ours_input']
+    if 'ours_grid' in record['ms_per_step']:
+        median = {name: entry['median']
+                  for name, entry in record['ms_per_step'].items()}
+        record['over_ours_grid'] = {
+            name: value / median['ours_grid']
+            for name, value in median.items() if name != 'ours_grid'}
+        # one record per configuration in the same file
+        name = '_'.join(f'{key}={value}' for key, value in
+                        record['config'].items())
+        records = {}
+        if arguments.out and os.path.exists(arguments.out):
+            with open(arguments.out) as file:
+                records = json.load(file)
+        records[name] = record
+        record = records
     print(json.dumps(record))
     if arguments.out:
         with open(arguments.out, 'w') as file:
@@ -445,12 +666,25 @@ def main():
         '--downsample_location', nargs='+', default=None,
         choices=('inference', 'loss', 'input'))
     parser.add_argument('--no-torch', action='store_true')
-    parser.add_argument('--serve', action='store_true', help=argparse.SUPPRESS)
+    parser.add_argument('--activation', choices=sorted(ACTIVATION_MODULES))
+    parser.add_argument('--channels', type=int)
+    parser.add_argument('--encoder_kernel_size', type=int)
+    parser.add_argument('--decoder_kernel_size', type=int)
+    parser.add_argument(
+        '--downsample_method', choices=('sum', 'average', 'max', 'center'))
+    parser.add_argument('--serve', nargs='?', const='trainer', default=None,
+                        choices=('trainer', 'seams'), help=argparse.SUPPRESS)
     arguments = parser.parse_args()
+    settings = {name: getattr(arguments, name) for name in GRID_FLAGS
+                if getattr(arguments, name) is not None}
     if arguments.serve:
-        return serve()
+        return serve(arguments.serve, settings)
     torch.cuda.set_device(0)
     batch = make_batch()
+    if settings:
+        if arguments.downsample_location:
+            parser.error('the grid flags train at the default location')
+        return compare(arguments, grid(arguments, batch, settings))
     if arguments.downsample_location:
         return compare(arguments, locations(arguments, batch))
     state = train.initial_state(emphases_amd.DEFAULT, seed=0)
