@@ -5,20 +5,23 @@ validate, save (`train/core.py:13-307`) - fed by `emphases_amd.data`; and
 `TorchModel`, the same architecture as a `torch.nn.Module` on the
 differentiable operator seams for the configurations the fused steps refuse.
 `TransformerModel` is the Transformer architecture on the same seams (the
-fused steps, `make_trainer` and `train` refuse it).  `EncoderTrainer` is the step of the models without a word decoder
-(downsample_location 'inference' and 'loss'); `make_trainer` picks the class.
-`PieceTrainer` is the step at downsample_location 'input' (every word a padded
-sequence of its own); `trainer_for` dispatches over all four locations.
-`GridTrainer` is the step of the reference's hyperparameter grid at
-'intermediate' (any activation, reduction, channel count and kernel size);
-`select_trainer` is `trainer_for` with `GridTrainer` behind it."""
+fused steps, `make_trainer` and `train` refuse it).
+
+The fused steps, one class per `downsample_location` and one behind them:
+`Trainer` ('intermediate'), `EncoderTrainer` ('inference' and 'loss', no word
+decoder), `PieceTrainer` ('input', every word a padded sequence of its own)
+and `GridTrainer` (the rest of the reference's hyperparameter grid at
+'intermediate').  `step_class` is the one dispatch, with every check made and
+nothing constructed; `select_trainer` builds what it names, `trainer_for` the
+same without the grid step, `make_trainer` without the piece step either."""
 from .core import (  # noqa: F401
-    PRECISIONS, Batch, EncoderTrainer, GridTrainer, PieceTrainer, Trainer, adam_state_dict, check_batch,
-    check_encoder_supported, check_grid_supported, check_pieces_supported,
-    check_precision,
-    check_supported,
-    checkpoint_names, gather_tables, initial_state, layer_names, make_trainer, parameter_offsets, split_layer_names, split_pack_tables,
-    select_trainer, trainer_for, write_checkpoint)
+    PRECISIONS, Batch, EncoderTrainer, GridTrainer, PieceTrainer, Trainer,
+    adam_state_dict, check_batch, check_encoder_supported,
+    check_grid_supported, check_pieces_supported, check_precision,
+    check_supported, checkpoint_names, gather_tables, initial_state,
+    layer_names, make_trainer, parameter_offsets, select_trainer,
+    split_layer_names, split_pack_tables, step_class, trainer_for,
+    write_checkpoint)
 from . import dropout  # noqa: F401
 from .model import (  # noqa: F401
     TorchModel, check_model_supported, initial_model_state, loss_fn)

@@ -57,6 +57,18 @@ regenerates the dropout masks in the backward.  `select_trainer` picks a
 specialised step where one covers the configuration - which then keeps its
 bits - and `GridTrainer` where none does.
 
+How the module is laid out.  What a step supports is data: `STEP_RULES`, one
+table of rules per class, walked by `refusal`; `step_class` is the one place
+that maps a downsample_location to a class (`STEP_OF_LOCATION`), and
+`select_trainer`, `trainer_for` and `make_trainer` are that dispatch with
+fewer candidates.  `_Step` holds the state, the batch layout, the workspace
+cache and every launch that more than one step issues; `_DecoderStep` is the
+one forward / backward skeleton of the three steps with a word decoder.  The
+classes differ by the methods they override - the reduce and its backward,
+the activation's backward, the buffers of their own - and by two entry-point
+names, never by a branch on the class: `Trainer` keeps its specialised
+kernels, `GridTrainer` the general ones, and neither stands in for the other.
+
 All parameters live in ONE flat device buffer in `weights.parameter_shapes`
 order (the order of `Model.parameters()`); gradients and the two Adam moments
 are buffers of the same shape.  The MFMA weight packs of the forward kernel
@@ -84,169 +96,100 @@ WORD_TILE = 32       # emph_conv1d on the word axis
 GRAD_TILE = 64       # emph_conv_weight_grad on either axis
 PRECISIONS = ('f32', 'bf16x3')
 SPLIT_CHANNELS = 80  # emph_conv1d_split, emph_conv_weight_grad_split
+GRID_CHANNELS = tuple(range(16, 129, 16))   # `TorchModel`'s rule
+GRID_KERNEL_SIZES = (1, 3, 5, 7)
+
+
+def _rules(**changes):
+    """The rules of a step, in the order they are tested: {field: (the
+    accepted values or a predicate, the text that names them)}.  `Trainer`'s,
+    with the fields of `changes` replaced (None: not tested) or appended."""
+    rules = {
+        'method': (('neural',), "'neural'"),
+        'architecture': (('convolution',), "'convolution'"),
+        'downsample_location': (('intermediate',), "'intermediate'"),
+        'downsample_method': (('sum', 'average'), "'sum' or 'average'"),
+        'activation': (('relu',), "'relu'"),
+        'loss': (('bce', 'mse'), "'bce' or 'mse'"),
+        'channels': ((80,), '80'),
+        'encoder_kernel_size': ((3,), '3'),
+        'decoder_kernel_size': ((3,), '3'),
+        'layers': (lambda layers: 0 <= layers <= 16, '0..16'),
+        'mel_feature': (bool, 'True (80..83 input features)')}
+    rules.update(changes)
+    return {field: rule for field, rule in rules.items() if rule is not None}
+
+
+_ALL_METHODS = (('sum', 'average', 'max', 'center'),
+                "'sum', 'average', 'max' or 'center'")
+# class -> (the step's name in a refusal, its rules)
+STEP_RULES = {
+    'Trainer': ('training step', _rules()),
+    'EncoderTrainer': ('encoder training step', _rules(
+        downsample_location=(('inference', 'loss'), "'inference' or 'loss'"),
+        downsample_method=None,
+        decoder_kernel_size=((3,), "3 (the output layer's kernel size)"))),
+    'PieceTrainer': ('piece training step', _rules(
+        downsample_location=(('input',), "'input'"),
+        downsample_method=_ALL_METHODS,
+        dropout=(lambda p: p is None,
+                 'None (no mask is specified for the piece layout)'))),
+    'GridTrainer': ('grid training step', _rules(
+        downsample_method=_ALL_METHODS,
+        activation=(('relu', 'gelu', 'silu', 'leaky_relu'),
+                    "'relu', 'gelu', 'silu' or 'leaky_relu'"),
+        channels=(GRID_CHANNELS, 'a multiple of 16 in 16..128'),
+        encoder_kernel_size=(GRID_KERNEL_SIZES, '1, 3, 5 or 7'),
+        decoder_kernel_size=(GRID_KERNEL_SIZES, '1, 3, 5 or 7'),
+        dropout=(lambda p: p is None or 0. <= p < 1.,
+                 'None or a probability 0 <= p < 1')))}
+# downsample_location -> the class of its specialised step
+STEP_OF_LOCATION = {
+    'intermediate': 'Trainer', 'inference': 'EncoderTrainer',
+    'loss': 'EncoderTrainer', 'input': 'PieceTrainer'}
+
+
+def refusal(step, config):
+    """What refuses `config` for the step of class `step`, naming the first
+    field outside its rules; None where the step covers it."""
+    name, rules = STEP_RULES[step]
+    for field, (accepted, supported) in rules.items():
+        value = getattr(config, field)
+        if not (accepted(value) if callable(accepted) else value in accepted):
+            return (f'the {name} supports {field} {supported} only, not '
+                    f'{field}={value!r}')
+    return None
+
+
+def _check(step, config):
+    message = refusal(step, config)
+    if message is not None:
+        raise NotImplementedError(message)
 
 
 def check_supported(config):
-    """NotImplementedError, naming the field, for a configuration the step does
-    not cover - before anything is allocated or launched."""
-    def refuse(field, supported):
-        raise NotImplementedError(
-            f'the training step supports {field} {supported} only, not '
-            f'{field}={getattr(config, field)!r}')
-    if config.method != 'neural':
-        refuse('method', "'neural'")
-    if config.architecture != 'convolution':
-        refuse('architecture', "'convolution'")
-    if config.downsample_location != 'intermediate':
-        refuse('downsample_location', "'intermediate'")
-    if config.downsample_method not in ('sum', 'average'):
-        refuse('downsample_method', "'sum' or 'average'")
-    if config.activation != 'relu':
-        refuse('activation', "'relu'")
-    if config.loss not in ('bce', 'mse'):
-        refuse('loss', "'bce' or 'mse'")
-    if config.channels != 80:
-        refuse('channels', '80')
-    if config.encoder_kernel_size != 3:
-        refuse('encoder_kernel_size', '3')
-    if config.decoder_kernel_size != 3:
-        refuse('decoder_kernel_size', '3')
-    if not 0 <= config.layers <= 16:
-        refuse('layers', '0..16')
-    if not config.mel_feature:
-        refuse('mel_feature', 'True (80..83 input features)')
+    """NotImplementedError, naming the field, for a configuration `Trainer`
+    does not cover - before anything is allocated or launched."""
+    _check('Trainer', config)
 
 
 def check_encoder_supported(config):
     """`check_supported` for `EncoderTrainer`: the models without a word
     decoder, downsample_location 'inference' or 'loss'."""
-    def refuse(field, supported):
-        raise NotImplementedError(
-            f'the encoder training step supports {field} {supported} only, '
-            f'not {field}={getattr(config, field)!r}')
-    if config.method != 'neural':
-        refuse('method', "'neural'")
-    if config.architecture != 'convolution':
-        refuse('architecture', "'convolution'")
-    if config.downsample_location not in ('inference', 'loss'):
-        refuse('downsample_location', "'inference' or 'loss'")
-    if config.activation != 'relu':
-        refuse('activation', "'relu'")
-    if config.loss not in ('bce', 'mse'):
-        refuse('loss', "'bce' or 'mse'")
-    if config.channels != 80:
-        refuse('channels', '80')
-    if config.encoder_kernel_size != 3:
-        refuse('encoder_kernel_size', '3')
-    if config.decoder_kernel_size != 3:
-        refuse('decoder_kernel_size', "3 (the output layer's kernel size)")
-    if not 0 <= config.layers <= 16:
-        refuse('layers', '0..16')
-    if not config.mel_feature:
-        refuse('mel_feature', 'True (80..83 input features)')
+    _check('EncoderTrainer', config)
 
 
 def check_pieces_supported(config):
     """`check_supported` for `PieceTrainer`: downsample_location 'input', all
     four reductions, no dropout."""
-    def refuse(field, supported):
-        raise NotImplementedError(
-            f'the piece training step supports {field} {supported} only, '
-            f'not {field}={getattr(config, field)!r}')
-    if config.method != 'neural':
-        refuse('method', "'neural'")
-    if config.architecture != 'convolution':
-        refuse('architecture', "'convolution'")
-    if config.downsample_location != 'input':
-        refuse('downsample_location', "'input'")
-    if config.downsample_method not in ('sum', 'average', 'max', 'center'):
-        refuse('downsample_method', "'sum', 'average', 'max' or 'center'")
-    if config.activation != 'relu':
-        refuse('activation', "'relu'")
-    if config.loss not in ('bce', 'mse'):
-        refuse('loss', "'bce' or 'mse'")
-    if config.channels != 80:
-        refuse('channels', '80')
-    if config.encoder_kernel_size != 3:
-        refuse('encoder_kernel_size', '3')
-    if config.decoder_kernel_size != 3:
-        refuse('decoder_kernel_size', '3')
-    if not 0 <= config.layers <= 16:
-        refuse('layers', '0..16')
-    if not config.mel_feature:
-        refuse('mel_feature', 'True (80..83 input features)')
-    if config.dropout is not None:
-        refuse('dropout', 'None (no mask is specified for the piece layout)')
-
-
-GRID_CHANNELS = tuple(range(16, 129, 16))   # `TorchModel`'s rule
-GRID_KERNEL_SIZES = (1, 3, 5, 7)
+    _check('PieceTrainer', config)
 
 
 def check_grid_supported(config):
     """`check_supported` for `GridTrainer`: the reference's hyperparameter
     grid at downsample_location 'intermediate' - any activation, reduction,
     channel count (a multiple of 16 up to 128) and odd kernel size up to 7."""
-    def refuse(field, supported):
-        raise NotImplementedError(
-            f'the grid training step supports {field} {supported} only, not '
-            f'{field}={getattr(config, field)!r}')
-    if config.method != 'neural':
-        refuse('method', "'neural'")
-    if config.architecture != 'convolution':
-        refuse('architecture', "'convolution'")
-    if config.downsample_location != 'intermediate':
-        refuse('downsample_location', "'intermediate'")
-    if config.downsample_method not in ('sum', 'average', 'max', 'center'):
-        refuse('downsample_method', "'sum', 'average', 'max' or 'center'")
-    if config.activation not in ('relu', 'gelu', 'silu', 'leaky_relu'):
-        refuse('activation', "'relu', 'gelu', 'silu' or 'leaky_relu'")
-    if config.loss not in ('bce', 'mse'):
-        refuse('loss', "'bce' or 'mse'")
-    if config.channels not in GRID_CHANNELS:
-        refuse('channels', 'a multiple of 16 in 16..128')
-    if config.encoder_kernel_size not in GRID_KERNEL_SIZES:
-        refuse('encoder_kernel_size', '1, 3, 5 or 7')
-    if config.decoder_kernel_size not in GRID_KERNEL_SIZES:
-        refuse('decoder_kernel_size', '1, 3, 5 or 7')
-    if not 0 <= config.layers <= 16:
-        refuse('layers', '0..16')
-    if not config.mel_feature:
-        refuse('mel_feature', 'True (80..83 input features)')
-    if config.dropout is not None and not 0. <= config.dropout < 1.:
-        refuse('dropout', 'None or a probability 0 <= p < 1')
-
-
-def check_grid_precision(precision):
-    """`check_precision` for `GridTrainer`: 'f32' only.  The split kernels of
-    'bf16x3' are Conv1d(80, 80, 3) with a ReLU flag and nothing else."""
-    if check_precision(precision) != 'f32':
-        raise NotImplementedError(
-            "the grid training step supports precision 'f32' only, not "
-            f'precision={precision!r}: the bf16 split kernels are '
-            'Conv1d(80, 80, 3) with ReLU')
-    return precision
-
-
-def _check_step(config):
-    """The check of the step that trains `config`: `PieceTrainer`'s at
-    downsample_location 'input', `Trainer`'s with a word decoder otherwise
-    (`GridTrainer`'s where that refuses), `EncoderTrainer`'s without one."""
-    if config.downsample_location == 'input':
-        check_pieces_supported(config)
-    elif config.has_decoder:
-        try:
-            check_supported(config)
-        except NotImplementedError:
-            try:
-                check_grid_supported(config)
-            except NotImplementedError:
-                pass
-            else:
-                return
-            raise
-    else:
-        check_encoder_supported(config)
+    _check('GridTrainer', config)
 
 
 def check_precision(precision):
@@ -268,22 +211,60 @@ def check_precision(precision):
         f'precision {precision!r} is not one of {sorted(engine.PRECISIONS)}')
 
 
+def check_grid_precision(precision):
+    """`check_precision` for `GridTrainer`: 'f32' only.  The split kernels of
+    'bf16x3' are Conv1d(80, 80, 3) with a ReLU flag and nothing else."""
+    if check_precision(precision) != 'f32':
+        raise NotImplementedError(
+            "the grid training step supports precision 'f32' only, not "
+            f'precision={precision!r}: the bf16 split kernels are '
+            'Conv1d(80, 80, 3) with ReLU')
+    return precision
+
+
+def step_class(config, precision=None, grid=True, locations=None):
+    """The class of the step that trains `config`, every check made and
+    nothing constructed: the specialised step of the configuration's location
+    first, `GridTrainer` where that refuses and `check_grid_supported` passes,
+    otherwise the specialised step's refusal.  `precision`: checked as well
+    unless None.  `grid=False`: never `GridTrainer`.  `locations`: the ones
+    the caller dispatches over; any other gets `Trainer`'s refusal of its
+    downsample_location.  The class is looked up in this module at the call."""
+    location = config.downsample_location
+    if locations is not None and location not in locations:
+        location = 'intermediate'
+    step, check = STEP_OF_LOCATION[location], check_precision
+    message = refusal(step, config)
+    if message is not None:
+        if not grid or refusal('GridTrainer', config) is not None:
+            raise NotImplementedError(message)
+        step, check = 'GridTrainer', check_grid_precision
+    if precision is not None:
+        check(precision)
+    return globals()[step]
+
+
 def split_layer_names(config):
     """The layers of `layer_names` that run on the bf16 pipe under
     precision='bf16x3': the Conv1d(80, 80, 3) on the frame axis (the input
     layer only when it has exactly 80 feature rows)."""
     names = ['input_layer'] if config.num_features == SPLIT_CHANNELS else []
-    return names + [f'frame_encoder.{2 * i}' for i in range(config.layers)]
+    return names + stack_names(config, 'frame_encoder')
+
+
+def stack_names(config, prefix):
+    """The conv layers of the stack `prefix` ('frame_encoder' or
+    'word_decoder'), in forward order: modules 0, 2, .. of its Sequential."""
+    return [f'{prefix}.{2 * i}' for i in range(config.layers)]
 
 
 def layer_names(config):
-    """The Conv1d(., 80, 3) layers in forward order (no word decoder at
+    """The conv layers in forward order (no word decoder at
     downsample_location 'inference' and 'loss', `model/core.py:28-30`)."""
-    prefixes = ('frame_encoder', 'word_decoder') if config.has_decoder else \
-        ('frame_encoder',)
-    return ['input_layer'] + [
-        f'{prefix}.{2 * i}' for prefix in prefixes
-        for i in range(config.layers)]
+    names = ['input_layer'] + stack_names(config, 'frame_encoder')
+    if config.has_decoder:
+        names += stack_names(config, 'word_decoder')
+    return names
 
 
 def checkpoint_names(config):
@@ -319,7 +300,7 @@ def initial_state(config=cfg.DEFAULT, seed=0):
     the reference's construction order (`model/core.py:16-37`,
     `model/layers/convolution.py:22-33`).  The caller's generator is left
     as it was."""
-    _check_step(config)
+    step_class(config)
     state = collections.OrderedDict()
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
@@ -344,6 +325,11 @@ def initial_state(config=cfg.DEFAULT, seed=0):
     return state
 
 
+def _tile_count(tiles):
+    """The rows of a device tile table (`Plan.tiles`)."""
+    return tiles.numel() // runtime.TILE_FIELDS
+
+
 def _pack_indices(indices):
     """`emph_conv_pack` of an index array [c_out, c_in, k] (int, < 2^24): the
     pack is a pure permutation with zero padding, so packing the indices + 1
@@ -359,7 +345,7 @@ def gather_tables(config=cfg.DEFAULT):
     packs (every layer) and of the data-gradient packs
     W'[ci][co][j] = W[co][ci][k - 1 - j] (every layer but the input layer,
     whose input needs no gradient)."""
-    _check_step(config)
+    step_class(config)
     offsets, _ = parameter_offsets(config)
     pieces, forward, backward = [], {}, {}
     cursor = 0
@@ -390,7 +376,7 @@ def split_pack_tables(config=cfg.DEFAULT):
     e of a pack is weight [32 m + lane % 32][16 block + 8 (lane / 32) + e]
     [tap] of its layer, -1 (zeros) for rows 80 .. 95: the layout of
     `emph_conv_split_pack`."""
-    _check_step(config)
+    step_class(config)
     offsets, _ = parameter_offsets(config)
     tap, block, m, lane, e = np.meshgrid(
         np.arange(3), np.arange(5), np.arange(3), np.arange(64), np.arange(8),
@@ -507,10 +493,12 @@ class Batch:
 
 
 class _Step:
-    """What `Trainer` and `EncoderTrainer` share: the flat state, the batch
-    layout, the frame encoder's launches, Adam and the checkpoint.  A
-    subclass names its `_check` and gives `_buffers`, `_forward` (whose
-    buffers' 'logits' then hold the packed word logits) and
+    """What every step shares: the flat state, the batch layout, Adam, the
+    checkpoint, the workspace (`_buffers`) and every launch that more than
+    one step issues - a conv layer and a conv stack forward and backward, the
+    frame encoder, the reduce, and the word tail (output layer, loss, output
+    layer's backward).  A subclass names its `_check` and gives `_forward`
+    (whose buffers' 'logits' then hold the packed word logits) and
     `_forward_backward` (which leaves the loss in `self.loss` and every
     gradient in `self.gradients`)."""
 
@@ -676,24 +664,41 @@ class _Step:
                 runtime.stream()), 'emph_gather_columns')
         return Batch(plan, meta, packed, packed_targets)
 
+    def _upload(self, tables):
+        """Host tables [(int32 array, {name: (first element, size)})], every
+        one a whole number of 16 bytes, in ONE copy to the device: the device
+        buffer and, per table, its views by name."""
+        host = np.concatenate([table for table, _ in tables])
+        with torch.cuda.device(self.device):
+            buffer = torch.from_numpy(host).to(self.device)
+        views, first = [], 0
+        for table, offsets in tables:
+            assert table.size % 4 == 0
+            views.append({
+                name: buffer[first + start:first + start + size]
+                for name, (start, size) in offsets.items()})
+            first += table.size
+        return buffer, views
+
     def metadata(self, plan):
         """The integer tables of a step for a packed layout on the device: one
         copy, views by name (`Batch.meta`)."""
         requests = [(runtime.AXIS_FRAMES, FRAME_TILE),
                     (runtime.AXIS_WORDS, WORD_TILE),
                     (runtime.AXIS_WORDS, GRAD_TILE)]
-        host, offsets = plan.pack_metadata(
-            list(dict.fromkeys(requests)), spans=self.precision == 'bf16x3')
-        with torch.cuda.device(self.device):
-            device_meta = torch.from_numpy(host).to(self.device)
-        meta = {name: device_meta[start:start + size]
-                for name, (start, size) in offsets.items()}
-        meta['_buffer'] = device_meta
+        buffer, (meta,) = self._upload([plan.pack_metadata(
+            list(dict.fromkeys(requests)), spans=self.precision == 'bf16x3')])
+        meta['_buffer'] = buffer
         return meta
+
+    def _frame_meta(self, batch):
+        """The tables of the layout the frame-rate layers run on."""
+        return batch.meta
 
     def _batch(self, arguments):
         if len(arguments) == 1 and isinstance(arguments[0], Batch):
-            if self._split_forward and 'conv_spans' not in arguments[0].meta:
+            meta = self._frame_meta(arguments[0])
+            if self._split_forward and 'conv_spans' not in meta:
                 raise ValueError(
                     "the batch was prepared by a trainer at precision='f32' "
                     "and carries no span table: prepare it with this "
@@ -722,13 +727,28 @@ class _Step:
     def _gradient(self, name):
         return self.gradients.data_ptr() + 4 * self.offsets[name][0]
 
-    def _conv(self, pack, bias, x, y, ld, c_in, activation, tiles, tile):
+    def _layer_shape(self, name):
+        """(c_in, kernel size) of conv layer `name`."""
+        _, shape = self.offsets[f'{name}.weight']
+        return shape[1], shape[2]
+
+    def _mask(self, name):
+        """(seed, stream, step) of the dropout mask of layer `name` at this
+        step (`train/dropout.py`)."""
+        return (self.seed & (1 << 64) - 1,
+                dropout_module.stream_of(self.config, name), self.steps)
+
+    def _conv(self, packs, name, bias, x, y, ld, activation, tiles, tile):
+        """`emph_conv1d` at the shape of layer `name` with its pack of
+        `packs`: the forward's, or the data gradient's (no input layer there,
+        so c_in is the layer's own either way)."""
+        c_in, kernel_size = self._layer_shape(name)
         runtime.check(self.lib.emph_conv1d(
             x.data_ptr(), ld, y.data_ptr(), ld,
-            self.packs.data_ptr() + 4 * pack[0], bias, c_in,
-            self.config.channels, 3, runtime.ACTIVATIONS[activation],
-            tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS, tile, 0,
-            runtime.stream()), 'emph_conv1d')
+            self.packs.data_ptr() + 4 * packs[name][0], bias, c_in,
+            self.config.channels, kernel_size,
+            runtime.ACTIVATIONS[activation], tiles.data_ptr(),
+            _tile_count(tiles), tile, 0, runtime.stream()), 'emph_conv1d')
 
     def _conv_split(self, pack, bias, x, y, ld, relu, spans):
         """One Conv1d(80, 80, 3) on the frame axis as bf16x3: a launch of
@@ -739,96 +759,248 @@ class _Step:
             1 if relu else 0, spans.data_ptr(), spans.numel() // 8, None,
             runtime.stream()), 'emph_conv1d_split')
 
-    def _frame_conv(self, name, x, y, ld, c_in, activation, batch):
-        """Forward of a frame-rate layer at the trainer's precision."""
+    def _layer(self, name, x, y, ld, activation, meta, axis, tile):
+        """Forward of conv layer `name` at the trainer's precision."""
+        bias = self._parameter(f'{name}.bias')
         if name in self._split_forward:
-            self._conv_split(
-                self._split_forward[name], self._parameter(f'{name}.bias'),
-                x, y, ld, activation == 'relu', batch.meta['conv_spans'])
+            self._conv_split(self._split_forward[name], bias, x, y, ld,
+                             activation == 'relu', meta['conv_spans'])
         else:
-            self._conv(
-                self._forward_packs[name], self._parameter(f'{name}.bias'),
-                x, y, ld, c_in, activation,
-                batch.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)],
-                FRAME_TILE)
+            self._conv(self._forward_packs, name, bias, x, y, ld, activation,
+                       meta[('tiles', axis, tile)], tile)
 
     def _dropout(self, name, y):
         """`torch.nn.Dropout` on the kept output of layer `name`, in place:
-        the mask of this layer at this step (`train/dropout.py`)."""
+        the mask of this layer at this step."""
         runtime.check(self.lib.emph_dropout(
-            y.data_ptr(), y.numel(), 0, self.dropout,
-            self.seed & (1 << 64) - 1,
-            dropout_module.stream_of(self.config, name), self.steps,
+            y.data_ptr(), y.numel(), 0, self.dropout, *self._mask(name),
             runtime.stream()), 'emph_dropout')
 
-    def _encoder_forward(self, batch, h, drop):
-        """input_layer and the frame encoder (model/core.py:91-94), every
-        layer's output kept: h[0] .. h[layers]."""
-        config, ld_f = self.config, batch.plan.ld_frames
-        self._frame_conv('input_layer', batch.features, h[0], ld_f,
-                         config.num_features, None, batch)
-        for i in range(config.layers):
-            name = f'frame_encoder.{2 * i}'
-            self._frame_conv(name, h[i], h[i + 1], ld_f, config.channels,
-                             'relu', batch)
+    def _forward_stack(self, meta, names, outputs, pre, ld, axis, tile,
+                       training):
+        """A conv stack (`model/layers/convolution.py:22-37`): outputs[i + 1]
+        = dropout(act(conv(outputs[i]))), every output kept.  `pre`: None, or
+        where the pre-activations are kept in training for an activation
+        whose derivative reads them - the activation is then a pass of its
+        own, which applies the mask too."""
+        activation = self.config.activation
+        drop = training and self.dropout > 0.
+        for i, name in enumerate(names):
+            if training and pre is not None:
+                self._layer(name, outputs[i], pre[i], ld, None, meta, axis,
+                            tile)
+                runtime.check(self.lib.emph_activation_dropout(
+                    pre[i].data_ptr(), outputs[i + 1].data_ptr(),
+                    pre[i].numel(), runtime.ACTIVATIONS[activation],
+                    self.dropout if drop else 0., *self._mask(name),
+                    runtime.stream()), 'emph_activation_dropout')
+                continue
+            self._layer(name, outputs[i], outputs[i + 1], ld, activation,
+                        meta, axis, tile)
             if drop:
-                self._dropout(name, h[i + 1])
+                self._dropout(name, outputs[i + 1])
 
-    def _backward_stack(self, batch, buffers, names, outputs, gradient, ld,
-                        grad_tiles, tiles, tile):
+    def _encoder_forward(self, view, buffers, training):
+        """input_layer and the frame encoder (model/core.py:91-94) on the
+        layout of `view`, every layer's output kept: buffers['frames'][0 ..
+        layers]."""
+        h, ld_f = buffers['frames'], view.plan.ld_frames
+        self._layer('input_layer', view.features, h[0], ld_f, None, view.meta,
+                    runtime.AXIS_FRAMES, FRAME_TILE)
+        self._forward_stack(
+            view.meta, stack_names(self.config, 'frame_encoder'), h,
+            buffers.get('pre_frames'), ld_f, runtime.AXIS_FRAMES, FRAME_TILE,
+            training)
+
+    def _segment_reduce(self, x, ld_x, bounds, table, segment, y, ld_y):
+        """The words y [channels, ld_y] of the frames x, `segment` naming the
+        table row of every word column."""
+        runtime.check(self.lib.emph_segment_reduce(
+            x.data_ptr(), ld_x, bounds.data_ptr(), y.data_ptr(), ld_y,
+            self.config.channels, table.data_ptr(), segment.data_ptr(), ld_y,
+            runtime.REDUCTIONS[self.config.downsample_method],
+            runtime.stream()), 'emph_segment_reduce')
+
+    def _reduce(self, view, batch, buffers):
+        """The encoder's output to the words (model/core.py:96-104):
+        buffers['words'][0]."""
+        meta = batch.meta
+        self._segment_reduce(
+            buffers['frames'][self.config.layers], batch.plan.ld_frames,
+            meta['bounds'], meta['table'], meta['word_segment'],
+            buffers['words'][0], batch.plan.ld_words)
+
+    def _word_logits(self, batch, words, buffers):
+        """output_layer on `words` [channels, ld_words] (model/core.py:138):
+        buffers['logits']."""
+        meta, ld_w = batch.meta, batch.plan.ld_words
+        runtime.check(self.lib.emph_output_layer(
+            words.data_ptr(), ld_w, self._parameter('output_layer.weight'),
+            self._parameter('output_layer.bias'), self.config.channels,
+            self.config.decoder_kernel_size, meta['table'].data_ptr(),
+            meta['word_segment'].data_ptr(), ld_w, runtime.AXIS_WORDS, 0,
+            buffers['logits'].data_ptr(), None, runtime.stream()),
+            'emph_output_layer')
+
+    _output_layer_backward = 'emph_output_layer_backward'
+
+    def _word_loss_backward(self, batch, words, buffers):
+        """The loss of buffers['logits'] on the words (train/core.py:315-353)
+        into `self.loss`, and output_layer's backward: its gradients and the
+        gradient of `words` in buffers['word_grad'][0]."""
+        config, ld_w = self.config, batch.plan.ld_words
+        word_segment, dlogit = batch.meta['word_segment'], buffers['dlogit']
+        runtime.check(self.lib.emph_loss_grad(
+            buffers['logits'].data_ptr(), batch.targets.data_ptr(),
+            word_segment.data_ptr(), ld_w, batch.plan.total_words,
+            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
+            dlogit.data_ptr(), runtime.stream()), 'emph_loss_grad')
+        entry = self._output_layer_backward
+        runtime.check(getattr(self.lib, entry)(
+            dlogit.data_ptr(), words.data_ptr(), ld_w,
+            self._parameter('output_layer.weight'), word_segment.data_ptr(),
+            config.channels, config.decoder_kernel_size, ld_w,
+            self._gradient('output_layer.weight'),
+            self._gradient('output_layer.bias'),
+            buffers['word_grad'][0].data_ptr(), ld_w, runtime.stream()), entry)
+
+    def _activation_backward(self, name, y, pre, dy):
+        """dy times the derivative of layer `name`'s activation (and its
+        dropout mask), in place: off the kept output `y`, which is zero where
+        ReLU or the mask cut."""
+        activation = runtime.ACTIVATIONS[self.config.activation]
+        if self.dropout > 0.:
+            runtime.check(self.lib.emph_activation_dropout_backward(
+                y.data_ptr(), dy.data_ptr(), dy.numel(), activation,
+                self.dropout, runtime.stream()),
+                'emph_activation_dropout_backward')
+        else:
+            runtime.check(self.lib.emph_activation_backward(
+                y.data_ptr(), dy.data_ptr(), dy.numel(), activation,
+                runtime.stream()), 'emph_activation_backward')
+
+    _weight_grad_kernel = 'emph_conv_weight_grad'
+
+    def _weight_grad(self, dy, x, ld, name, tiles, buffers):
+        entry = 'emph_conv_weight_grad_split' \
+            if name in self._split_forward else self._weight_grad_kernel
+        c_in, kernel_size = self._layer_shape(name)
+        runtime.check(getattr(self.lib, entry)(
+            dy.data_ptr(), ld, x.data_ptr(), ld, c_in, self.config.channels,
+            kernel_size, tiles.data_ptr(), _tile_count(tiles), GRAD_TILE,
+            buffers['slabs'].data_ptr(), self._gradient(f'{name}.weight'),
+            self._gradient(f'{name}.bias'), runtime.stream()), entry)
+
+    def _backward_stack(self, meta, buffers, names, outputs, pre, gradient,
+                        ld, axis, tile):
         """Backward of a conv stack, from the gradient of the last output
         (gradient[0]) down to the gradient of outputs[0]; returns the buffer
         that holds it."""
-        lib, channels, stream = self.lib, self.config.channels, runtime.stream()
+        grad_tiles = meta[('tiles', axis, GRAD_TILE)]
         current = 0
         for i in range(len(names) - 1, -1, -1):
             name = names[i]
             dy = gradient[current]
-            if self.dropout > 0.:
-                runtime.check(lib.emph_activation_dropout_backward(
-                    outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
-                    runtime.ACTIVATIONS['relu'], self.dropout, stream),
-                    'emph_activation_dropout_backward')
-            else:
-                runtime.check(lib.emph_activation_backward(
-                    outputs[i + 1].data_ptr(), dy.data_ptr(), dy.numel(),
-                    runtime.ACTIVATIONS['relu'], stream),
-                    'emph_activation_backward')
-            self._weight_grad(dy, outputs[i], ld, channels, name,
-                              grad_tiles, buffers)
+            self._activation_backward(
+                name, outputs[i + 1], None if pre is None else pre[i], dy)
+            self._weight_grad(dy, outputs[i], ld, name, grad_tiles, buffers)
             if name in self._split_backward:
                 self._conv_split(
-                    self._split_backward[name],
-                    self._zero_bias.data_ptr(), dy, gradient[1 - current],
-                    ld, False, batch.meta['conv_spans'])
+                    self._split_backward[name], self._zero_bias.data_ptr(),
+                    dy, gradient[1 - current], ld, False, meta['conv_spans'])
             else:
-                self._conv(self._backward_packs[name], None, dy,
-                           gradient[1 - current], ld, channels, None,
-                           tiles, tile)
+                self._conv(self._backward_packs, name, None, dy,
+                           gradient[1 - current], ld, None,
+                           meta[('tiles', axis, tile)], tile)
             current = 1 - current
         return gradient[current]
 
-    def _encoder_backward(self, batch, buffers):
+    def _encoder_backward(self, view, buffers):
         """From the gradient of the encoder's output (buffers['frame_grad'][0])
         to the gradients of the frame encoder and the input layer."""
-        config, ld_f = self.config, batch.plan.ld_frames
-        frame_tiles = batch.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
-        encoder = [f'frame_encoder.{2 * i}' for i in range(config.layers)]
+        ld_f = view.plan.ld_frames
         dinput = self._backward_stack(
-            batch, buffers, encoder, buffers['frames'], buffers['frame_grad'],
-            ld_f, frame_tiles, frame_tiles, FRAME_TILE)
-        self._weight_grad(dinput, batch.features, ld_f, config.num_features,
-                          'input_layer', frame_tiles, buffers)
+            view.meta, buffers, stack_names(self.config, 'frame_encoder'),
+            buffers['frames'], buffers.get('pre_frames'),
+            buffers['frame_grad'], ld_f, runtime.AXIS_FRAMES, FRAME_TILE)
+        self._weight_grad(
+            dinput, view.features, ld_f, 'input_layer',
+            view.meta[('tiles', runtime.AXIS_FRAMES, GRAD_TILE)], buffers)
 
-    def _weight_grad(self, dy, x, ld, c_in, name, tiles, buffers):
-        split = name in self._split_forward
-        entry = 'emph_conv_weight_grad_split' if split else \
-            'emph_conv_weight_grad'
-        runtime.check(getattr(self.lib, entry)(
-            dy.data_ptr(), ld, x.data_ptr(), ld, c_in, self.config.channels, 3,
-            tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS, GRAD_TILE,
-            buffers['slabs'].data_ptr(), self._gradient(f'{name}.weight'),
-            self._gradient(f'{name}.bias'), runtime.stream()), entry)
+    def _reduce_backward(self, view, batch, buffers, dword):
+        """The gradient `dword` of buffers['words'][0] back through the
+        reduce, into buffers['frame_grad'][0]: every reduction (max reads the
+        encoder's output and the pooled words, both kept)."""
+        meta, plan = batch.meta, batch.plan
+        tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        runtime.check(self.lib.emph_segment_reduce_backward(
+            dword.data_ptr(), plan.ld_words, meta['bounds'].data_ptr(),
+            buffers['frames'][self.config.layers].data_ptr(), plan.ld_frames,
+            buffers['words'][0].data_ptr(),
+            buffers['frame_grad'][0].data_ptr(), plan.ld_frames,
+            self.config.channels, meta['table'].data_ptr(), tiles.data_ptr(),
+            _tile_count(tiles),
+            runtime.REDUCTIONS[self.config.downsample_method],
+            runtime.stream()), 'emph_segment_reduce_backward')
+
+    ###########################################################################
+    # Workspace
+    ###########################################################################
+
+    def _frame_plan(self, plan):
+        """The layout the frame-rate layers run on."""
+        return plan
+
+    def _workspace_needs(self, frame_tiles, word_tiles):
+        """{name: number}: what of a layout's tile counts the sizes of the
+        buffers depend on (part of the cache key)."""
+        counts = (frame_tiles, word_tiles) if self.config.has_decoder else \
+            (frame_tiles,)
+        return {'parts': max(
+            int(self.lib.emph_conv_weight_grad_parts(n)) for n in counts)}
+
+    def _slab_floats(self, needs):
+        """The size of 'slabs', the workspace of the weight gradients."""
+        channels = self.config.channels
+        slab = channels * 3 * self.config.num_features + channels
+        return max(needs['parts'], 1) * slab
+
+    _buffer_dtypes = {}     # name -> dtype of the buffers that are not float32
+
+    def _buffer_shapes(self, ld_frames, ld_words, needs):
+        """{name: shape} of the step's buffers, in the order in which they
+        are allocated."""
+        channels, layers = self.config.channels, self.config.layers
+        decoder = self.config.has_decoder
+        return {
+            'frames': (layers + 1, channels, ld_frames),
+            'words': (layers + 1 if decoder else 1, channels, ld_words),
+            'frame_grad': (2, channels, ld_frames),
+            'word_grad': (2 if decoder else 1, channels, ld_words),
+            'logits': (ld_words,),
+            'dlogit': (ld_words,),
+            'slabs': (self._slab_floats(needs),)}
+
+    def _buffers(self, plan, frame_plan=None):
+        """The activations and gradients of a step for a packed layout, kept
+        between steps (zero at first, so that padding columns stay finite);
+        one set at a time."""
+        frame_plan = frame_plan or self._frame_plan(plan)
+        needs = self._workspace_needs(
+            len(frame_plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE)),
+            len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE)))
+        ld_frames, ld_words = frame_plan.ld_frames, plan.ld_words
+        key = (ld_frames, ld_words) + tuple(needs.values())
+        found = self._workspace.get(key)
+        if found is None:
+            self._workspace.clear()
+            shapes = self._buffer_shapes(ld_frames, ld_words, needs)
+            found = self._workspace[key] = {
+                name: torch.zeros(
+                    shape, dtype=self._buffer_dtypes.get(name, torch.float32),
+                    device=self.device)
+                for name, shape in shapes.items()}
+        return found
 
     ###########################################################################
     # API
@@ -878,115 +1050,70 @@ class _Step:
         return loss
 
 
-class Trainer(_Step):
+class _DecoderStep(_Step):
+    """The step of the models with a word decoder, in the order of
+    `model/core.py:41-107,138` and back: input layer, frame encoder, reduce,
+    word decoder, output layer, loss, and their backwards in reverse.  A
+    subclass overrides the launches that are its own: `_enter`, `_reduce` and
+    `_reduce_backward`, `_activation_backward`, the two entry points
+    `_weight_grad_kernel` and `_output_layer_backward`, and its buffers."""
+
+    def _enter(self, batch):
+        """(the step's buffers, the batch as the frame-rate layers see it)."""
+        return self._buffers(batch.plan), batch
+
+    def _forward_view(self, batch, training):
+        config, ld_w = self.config, batch.plan.ld_words
+        buffers, view = self._enter(batch)
+        d = buffers['words']
+        # ---- forward, every layer's output kept (model/core.py:91-107,138)
+        self._encoder_forward(view, buffers, training)
+        self._reduce(view, batch, buffers)
+        self._forward_stack(
+            batch.meta, stack_names(config, 'word_decoder'), d,
+            buffers.get('pre_words'), ld_w, runtime.AXIS_WORDS, WORD_TILE,
+            training)
+        self._word_logits(batch, d[config.layers], buffers)
+        return buffers, view
+
+    def _forward(self, batch, training=False):
+        """The forward launches of a step; returns the step's buffers, whose
+        'logits' then hold the packed logits [ld_words].  `training`: the
+        train-mode forward, which keeps what the backward reads and applies
+        the dropout masks of the step (never for validation)."""
+        return self._forward_view(batch, training)[0]
+
+    def _forward_backward(self, batch):
+        config, ld_w = self.config, batch.plan.ld_words
+        buffers, view = self._forward_view(batch, True)
+        d = buffers['words']
+        # ---- loss (train/core.py:315-353) and backward
+        self._word_loss_backward(batch, d[config.layers], buffers)
+        dword = self._backward_stack(
+            batch.meta, buffers, stack_names(config, 'word_decoder'), d,
+            buffers.get('pre_words'), buffers['word_grad'], ld_w,
+            runtime.AXIS_WORDS, WORD_TILE)
+        self._reduce_backward(view, batch, buffers, dword)
+        self._encoder_backward(view, buffers)
+
+
+class Trainer(_DecoderStep):
     """`Trainer(...).step(*batch[:5])` is one iteration of the reference's loop
     (`train/core.py:105-142`) for the convolution model; see the module
     docstring for the two deviations."""
 
-    def _buffers(self, plan):
-        """The activations and gradients of a step for a packed layout, kept
-        between steps (zero at first, so that padding columns stay finite)."""
-        frame_tiles = len(plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
-        word_tiles = len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE))
-        parts = max(
-            int(self.lib.emph_conv_weight_grad_parts(n))
-            for n in (frame_tiles, word_tiles))
-        key = (plan.ld_frames, plan.ld_words, parts)
-        found = self._workspace.get(key)
-        if found is None:
-            self._workspace.clear()
-            channels, layers = self.config.channels, self.config.layers
-            zeros = lambda *shape: torch.zeros(  # noqa: E731
-                shape, dtype=torch.float32, device=self.device)
-            slab = channels * 3 * self.config.num_features + channels
-            found = {
-                'frames': zeros(layers + 1, channels, plan.ld_frames),
-                'words': zeros(layers + 1, channels, plan.ld_words),
-                'frame_grad': zeros(2, channels, plan.ld_frames),
-                'word_grad': zeros(2, channels, plan.ld_words),
-                'logits': zeros(plan.ld_words),
-                'dlogit': zeros(plan.ld_words),
-                'slabs': zeros(max(parts, 1) * slab)}
-            self._workspace[key] = found
-        return found
-
-    def _forward(self, batch, training=False):
-        """The forward launches of a step; returns the step's buffers, whose
-        'logits' then hold the packed logits [ld_words].  `training`: with
-        the dropout masks of the step (never for validation)."""
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        ld_f, ld_w = plan.ld_frames, plan.ld_words
-        frames, words = runtime.AXIS_FRAMES, runtime.AXIS_WORDS
-        buffers = self._buffers(plan)
-        stream = runtime.stream()
-        drop = training and self.dropout > 0.
-        word_tiles = meta[('tiles', words, WORD_TILE)]
-        table, bounds = meta['table'], meta['bounds']
-        word_segment = meta['word_segment']
-        mode = runtime.REDUCTIONS[config.downsample_method]
-        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
-
-        # ---- forward, every layer's output kept (model/core.py:91-107,138)
-        h, d = buffers['frames'], buffers['words']
-        self._encoder_forward(batch, h, drop)
-        runtime.check(lib.emph_segment_reduce(
-            h[layers].data_ptr(), ld_f, bounds.data_ptr(), d[0].data_ptr(),
-            ld_w, channels, table.data_ptr(), word_segment.data_ptr(), ld_w,
-            mode, stream), 'emph_segment_reduce')
-        for i, name in enumerate(decoder):
-            self._conv(self._forward_packs[name],
-                       self._parameter(f'{name}.bias'), d[i], d[i + 1], ld_w,
-                       channels, 'relu', word_tiles, WORD_TILE)
-            if drop:
-                self._dropout(name, d[i + 1])
-        logits = buffers['logits']
-        runtime.check(lib.emph_output_layer(
-            d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
-            self._parameter('output_layer.bias'), channels, 3,
-            table.data_ptr(), word_segment.data_ptr(), ld_w, words, 0,
-            logits.data_ptr(), None, stream), 'emph_output_layer')
-        return buffers
-
-    def _forward_backward(self, batch):
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        ld_f, ld_w = plan.ld_frames, plan.ld_words
-        buffers = self._forward(batch, training=True)
-        stream = runtime.stream()
-        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
-        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
-        word_grad_tiles = meta[('tiles', runtime.AXIS_WORDS, GRAD_TILE)]
-        table, bounds = meta['table'], meta['bounds']
-        word_segment = meta['word_segment']
-        mode = runtime.REDUCTIONS[config.downsample_method]
-        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
-        d = buffers['words']
-        logits, dlogit = buffers['logits'], buffers['dlogit']
-
-        # ---- loss (train/core.py:315-353) and backward
-        runtime.check(lib.emph_loss_grad(
-            logits.data_ptr(), batch.targets.data_ptr(),
-            word_segment.data_ptr(), ld_w, plan.total_words,
-            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
-            dlogit.data_ptr(), stream), 'emph_loss_grad')
-        dd, dh = buffers['word_grad'], buffers['frame_grad']
-        runtime.check(lib.emph_output_layer_backward(
-            dlogit.data_ptr(), d[layers].data_ptr(), ld_w,
-            self._parameter('output_layer.weight'), word_segment.data_ptr(),
-            channels, 3, ld_w, self._gradient('output_layer.weight'),
-            self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
-            stream), 'emph_output_layer_backward')
-
-        dword = self._backward_stack(
-            batch, buffers, decoder, d, dd, ld_w, word_grad_tiles, word_tiles,
-            WORD_TILE)
-        runtime.check(lib.emph_segment_broadcast(
-            dword.data_ptr(), ld_w, bounds.data_ptr(), dh[0].data_ptr(), ld_f,
-            channels, table.data_ptr(), frame_tiles.data_ptr(),
-            frame_tiles.numel() // runtime.TILE_FIELDS, mode, stream),
-            'emph_segment_broadcast')
-        self._encoder_backward(batch, buffers)
+    def _reduce_backward(self, view, batch, buffers, dword):
+        """'sum' and 'average' need nothing kept: every frame takes its
+        word's gradient."""
+        meta, plan = batch.meta, batch.plan
+        tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        runtime.check(self.lib.emph_segment_broadcast(
+            dword.data_ptr(), plan.ld_words, meta['bounds'].data_ptr(),
+            buffers['frame_grad'][0].data_ptr(), plan.ld_frames,
+            self.config.channels, meta['table'].data_ptr(), tiles.data_ptr(),
+            _tile_count(tiles),
+            runtime.REDUCTIONS[self.config.downsample_method],
+            runtime.stream()), 'emph_segment_broadcast')
 
 
 class EncoderTrainer(_Step):
@@ -999,35 +1126,26 @@ class EncoderTrainer(_Step):
 
     _check = staticmethod(check_encoder_supported)
 
-    def _buffers(self, plan):
-        """The activations and gradients of a step for a packed layout, kept
-        between steps (zero at first, so that padding columns stay finite)."""
-        frame_tiles = len(plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
-        parts = int(self.lib.emph_conv_weight_grad_parts(frame_tiles))
-        head_parts = int(self.lib.emph_frame_head_parts(frame_tiles))
-        key = (plan.ld_frames, plan.ld_words, parts, head_parts, frame_tiles)
-        found = self._workspace.get(key)
-        if found is None:
-            self._workspace.clear()
-            channels, layers = self.config.channels, self.config.layers
-            zeros = lambda *shape, dtype=torch.float32: torch.zeros(  # noqa: E731
-                shape, dtype=dtype, device=self.device)
-            slab = channels * 3 * self.config.num_features + channels
-            found = {
-                'frames': zeros(layers + 1, channels, plan.ld_frames),
-                'words': zeros(1, channels, plan.ld_words),
-                'frame_grad': zeros(2, channels, plan.ld_frames),
-                'word_grad': zeros(1, channels, plan.ld_words),
-                'logits': zeros(plan.ld_words),
-                'dlogit': zeros(plan.ld_words),
-                'frame_logits': zeros(plan.ld_frames),
-                'frame_dlogit': zeros(plan.ld_frames),
-                'partials': zeros(max(frame_tiles, 1), dtype=torch.float64),
-                'slabs': zeros(max(
-                    max(parts, 1) * slab,
-                    max(head_parts, 1) * (3 * channels + 1)))}
-            self._workspace[key] = found
-        return found
+    def _workspace_needs(self, frame_tiles, word_tiles):
+        return dict(
+            super()._workspace_needs(frame_tiles, word_tiles),
+            head_parts=int(self.lib.emph_frame_head_parts(frame_tiles)),
+            frame_tiles=frame_tiles)
+
+    def _slab_floats(self, needs):
+        """... and of the frame head's backward."""
+        return max(
+            super()._slab_floats(needs),
+            max(needs['head_parts'], 1) * (3 * self.config.channels + 1))
+
+    _buffer_dtypes = {'partials': torch.float64}
+
+    def _buffer_shapes(self, ld_frames, ld_words, needs):
+        shapes = super()._buffer_shapes(ld_frames, ld_words, needs)
+        slabs = shapes.pop('slabs')
+        return dict(
+            shapes, frame_logits=(ld_frames,), frame_dlogit=(ld_frames,),
+            partials=(max(needs['frame_tiles'], 1),), slabs=slabs)
 
     def _forward(self, batch, training=False):
         """The forward launches; returns the step's buffers.  In training at
@@ -1036,36 +1154,21 @@ class EncoderTrainer(_Step):
         locations in eval mode, `model/core.py:109-138` - their 'logits' hold
         the packed word logits [ld_words].  `training`: with the dropout
         masks of the step."""
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        ld_f, ld_w = plan.ld_frames, plan.ld_words
-        buffers = self._buffers(plan)
-        stream = runtime.stream()
-        h = buffers['frames']
-        self._encoder_forward(batch, h, training and self.dropout > 0.)
+        config, layers = self.config, self.config.layers
+        buffers = self._buffers(batch.plan)
+        self._encoder_forward(batch, buffers, training)
         if training and config.downsample_location == 'inference':
-            tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
-            runtime.check(lib.emph_frame_head(
-                h[layers].data_ptr(), ld_f,
+            tiles = batch.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+            runtime.check(self.lib.emph_frame_head(
+                buffers['frames'][layers].data_ptr(), batch.plan.ld_frames,
                 self._parameter('output_layer.weight'),
-                self._parameter('output_layer.bias'), channels, 3,
-                tiles.data_ptr(), tiles.numel() // runtime.TILE_FIELDS,
-                buffers['frame_logits'].data_ptr(), stream), 'emph_frame_head')
+                self._parameter('output_layer.bias'), config.channels, 3,
+                tiles.data_ptr(), _tile_count(tiles),
+                buffers['frame_logits'].data_ptr(), runtime.stream()),
+                'emph_frame_head')
             return buffers
-        table, word_segment = meta['table'], meta['word_segment']
-        d = buffers['words']
-        runtime.check(lib.emph_segment_reduce(
-            h[layers].data_ptr(), ld_f, meta['bounds'].data_ptr(),
-            d[0].data_ptr(), ld_w, channels, table.data_ptr(),
-            word_segment.data_ptr(), ld_w,
-            runtime.REDUCTIONS[config.downsample_method], stream),
-            'emph_segment_reduce')
-        runtime.check(lib.emph_output_layer(
-            d[0].data_ptr(), ld_w, self._parameter('output_layer.weight'),
-            self._parameter('output_layer.bias'), channels, 3,
-            table.data_ptr(), word_segment.data_ptr(), ld_w,
-            runtime.AXIS_WORDS, 0, buffers['logits'].data_ptr(), None, stream),
-            'emph_output_layer')
+        self._reduce(batch, batch, buffers)
+        self._word_logits(batch, buffers['words'][0], buffers)
         return buffers
 
     def _forward_backward(self, batch):
@@ -1073,9 +1176,7 @@ class EncoderTrainer(_Step):
         channels, layers = config.channels, config.layers
         ld_f, ld_w = plan.ld_frames, plan.ld_words
         frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
-        n_tiles = frame_tiles.numel() // runtime.TILE_FIELDS
-        table, bounds = meta['table'], meta['bounds']
-        word_segment = meta['word_segment']
+        n_tiles = _tile_count(frame_tiles)
         if config.downsample_location == 'inference' and \
                 (len(plan.words) == 0 or int(min(plan.words)) < 1):
             raise ValueError(
@@ -1089,7 +1190,7 @@ class EncoderTrainer(_Step):
             logits, dlogit = buffers['frame_logits'], buffers['frame_dlogit']
             runtime.check(lib.emph_frame_loss_grad(
                 logits.data_ptr(), batch.targets.data_ptr(),
-                bounds.data_ptr(), ld_w, table.data_ptr(),
+                meta['bounds'].data_ptr(), ld_w, meta['table'].data_ptr(),
                 frame_tiles.data_ptr(), n_tiles, plan.total_frames,
                 runtime.BCE_FORMS[config.loss],
                 runtime.UPSAMPLE_METHODS[config.upsample_method],
@@ -1105,26 +1206,9 @@ class EncoderTrainer(_Step):
         else:
             # ---- loss on the words (train/core.py:341-353), the head and
             # the reduce
-            d, dd = buffers['words'], buffers['word_grad']
-            logits, dlogit = buffers['logits'], buffers['dlogit']
-            runtime.check(lib.emph_loss_grad(
-                logits.data_ptr(), batch.targets.data_ptr(),
-                word_segment.data_ptr(), ld_w, plan.total_words,
-                runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
-                dlogit.data_ptr(), stream), 'emph_loss_grad')
-            runtime.check(lib.emph_output_layer_backward(
-                dlogit.data_ptr(), d[0].data_ptr(), ld_w,
-                self._parameter('output_layer.weight'),
-                word_segment.data_ptr(), channels, 3, ld_w,
-                self._gradient('output_layer.weight'),
-                self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
-                stream), 'emph_output_layer_backward')
-            runtime.check(lib.emph_segment_reduce_backward(
-                dd[0].data_ptr(), ld_w, bounds.data_ptr(),
-                h[layers].data_ptr(), ld_f, d[0].data_ptr(), dh[0].data_ptr(),
-                ld_f, channels, table.data_ptr(), frame_tiles.data_ptr(),
-                n_tiles, runtime.REDUCTIONS[config.downsample_method], stream),
-                'emph_segment_reduce_backward')
+            self._word_loss_backward(batch, buffers['words'][0], buffers)
+            self._reduce_backward(
+                batch, batch, buffers, buffers['word_grad'][0])
         self._encoder_backward(batch, buffers)
 
 
@@ -1144,175 +1228,86 @@ class PieceTrainer(Trainer):
         the gather table, the piece bounds, `word_piece` and `piece_column` -
         all in ONE copy to the device."""
         pieces = plan.pieces(self.config.downsample_method)
-        tile = (runtime.AXIS_FRAMES, FRAME_TILE)
-        word_host, word_offsets = plan.pack_metadata(list(dict.fromkeys(
-            [(runtime.AXIS_WORDS, WORD_TILE), (runtime.AXIS_WORDS, GRAD_TILE)])))
-        piece_host, piece_offsets = pieces.plan.pack_metadata(
-            list(dict.fromkeys([tile, (runtime.AXIS_FRAMES, GRAD_TILE)])),
-            spans=self.precision == 'bf16x3')
-        extras = [('gather', pieces.gather.view(np.int32).ravel()),
-                  ('piece_bounds', pieces.bounds.ravel()),
-                  ('word_piece', pieces.word_piece),
-                  ('piece_column', pieces.piece_column)]
+        tables = [
+            plan.pack_metadata(list(dict.fromkeys(
+                [(runtime.AXIS_WORDS, WORD_TILE),
+                 (runtime.AXIS_WORDS, GRAD_TILE)]))),
+            pieces.plan.pack_metadata(
+                list(dict.fromkeys([(runtime.AXIS_FRAMES, FRAME_TILE),
+                                    (runtime.AXIS_FRAMES, GRAD_TILE)])),
+                spans=self.precision == 'bf16x3')]
         # (every part starts on a 16-byte boundary, the int64 tables included)
-        parts, cursor, extra_offsets = [word_host, piece_host], \
-            word_host.size + piece_host.size, {}
-        assert word_host.size % 4 == 0 and piece_host.size % 4 == 0
-        for name, array in extras:
-            extra_offsets[name] = (cursor, array.size)
+        for name, array in (('gather', pieces.gather.view(np.int32).ravel()),
+                            ('piece_bounds', pieces.bounds.ravel()),
+                            ('word_piece', pieces.word_piece),
+                            ('piece_column', pieces.piece_column)):
             padded = np.zeros(-(-max(array.size, 1) // 4) * 4, dtype=np.int32)
             padded[:array.size] = array
-            parts.append(padded)
-            cursor += padded.size
-        host = np.concatenate(parts)
-        with torch.cuda.device(self.device):
-            device_meta = torch.from_numpy(host).to(self.device)
-        meta = {name: device_meta[start:start + size]
-                for name, (start, size) in word_offsets.items()}
-        piece_meta = {
-            name: device_meta[word_host.size + start:][:size]
-            for name, (start, size) in piece_offsets.items()}
-        piece_meta.update(
-            (name, device_meta[start:start + size])
-            for name, (start, size) in extra_offsets.items())
+            tables.append((padded, {name: (0, array.size)}))
+        buffer, (meta, piece_meta, *extras) = self._upload(tables)
+        for extra in extras:
+            piece_meta.update(extra)
         piece_meta['plan'] = pieces.plan
         meta['pieces'] = piece_meta
-        meta['_buffer'] = device_meta
+        meta['_buffer'] = buffer
         return meta
 
-    def _batch(self, arguments):
-        if len(arguments) == 1 and isinstance(arguments[0], Batch):
-            pieces = arguments[0].meta.get('pieces')
-            if pieces is None:
-                raise ValueError(
-                    'the batch carries no piece tables: prepare it with this '
-                    "trainer (downsample_location='input')")
-            if self._split_forward and 'conv_spans' not in pieces:
-                raise ValueError(
-                    "the batch was prepared by a trainer at precision='f32' "
-                    "and carries no span table: prepare it with this "
-                    f"trainer (precision={self.precision!r})")
-            return arguments[0]
-        return self.prepare(*arguments)
+    def _frame_meta(self, batch):
+        pieces = batch.meta.get('pieces')
+        if pieces is None:
+            raise ValueError(
+                'the batch carries no piece tables: prepare it with this '
+                "trainer (downsample_location='input')")
+        return pieces
 
-    def _buffers(self, plan, piece_plan=None):
-        """The activations and gradients of a step, kept between steps (zero
-        at first, so that padding columns stay finite): the frame-rate ones on
-        the piece layout, the word-rate ones on the batch's own."""
-        if piece_plan is None:
-            piece_plan = plan.pieces(self.config.downsample_method).plan
-        frame_tiles = len(piece_plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
-        word_tiles = len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE))
-        parts = max(
-            int(self.lib.emph_conv_weight_grad_parts(n))
-            for n in (frame_tiles, word_tiles))
-        key = (piece_plan.ld_frames, plan.ld_words, parts)
-        found = self._workspace.get(key)
-        if found is None:
-            self._workspace.clear()
-            channels, layers = self.config.channels, self.config.layers
-            zeros = lambda *shape: torch.zeros(  # noqa: E731
-                shape, dtype=torch.float32, device=self.device)
-            slab = channels * 3 * self.config.num_features + channels
-            found = {
-                'piece_features': zeros(
-                    self.config.num_features, piece_plan.ld_frames),
-                'frames': zeros(layers + 1, channels, piece_plan.ld_frames),
-                'words': zeros(layers + 1, channels, plan.ld_words),
-                'frame_grad': zeros(2, channels, piece_plan.ld_frames),
-                'word_grad': zeros(2, channels, plan.ld_words),
-                'logits': zeros(plan.ld_words),
-                'dlogit': zeros(plan.ld_words),
-                'slabs': zeros(max(parts, 1) * slab)}
-            self._workspace[key] = found
-        return found
+    def _frame_plan(self, plan):
+        return plan.pieces(self.config.downsample_method).plan
 
-    def _forward(self, batch, training=False):
-        """The forward launches of a step (`model/core.py:41-87,138`); returns
-        the step's buffers, whose 'logits' then hold the packed logits
-        [ld_words] and whose 'view' is the batch on the piece layout."""
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        pieces = meta['pieces']
+    def _buffer_shapes(self, ld_frames, ld_words, needs):
+        """The frame-rate buffers are on the piece layout, the word-rate ones
+        on the batch's own; 'piece_features': the features gathered there."""
+        return {'piece_features': (self.config.num_features, ld_frames),
+                **super()._buffer_shapes(ld_frames, ld_words, needs)}
+
+    def _enter(self, batch):
+        """Gathers the features into the piece layout (`model/core.py:41-87`):
+        the view is the batch there."""
+        pieces = batch.meta['pieces']
         piece_plan = pieces['plan']
-        ld_f, ld_w, ld_p = plan.ld_frames, plan.ld_words, piece_plan.ld_frames
-        buffers = self._buffers(plan, piece_plan)
-        stream = runtime.stream()
-        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
-        table, word_segment = meta['table'], meta['word_segment']
-        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
-
+        buffers = self._buffers(batch.plan, piece_plan)
         gathered = buffers['piece_features']
-        runtime.check(lib.emph_gather_columns(
-            batch.features.data_ptr(), ld_f, gathered.data_ptr(), ld_p,
-            config.num_features, pieces['gather'].data_ptr(), len(piece_plan),
-            stream), 'emph_gather_columns')
-        view = buffers['view'] = Batch(piece_plan, pieces, gathered, None)
-        h, d = buffers['frames'], buffers['words']
-        self._encoder_forward(view, h, False)
-        runtime.check(lib.emph_segment_reduce(
-            h[layers].data_ptr(), ld_p, pieces['piece_bounds'].data_ptr(),
-            d[0].data_ptr(), ld_w, channels, pieces['table'].data_ptr(),
-            pieces['word_piece'].data_ptr(), ld_w,
-            runtime.REDUCTIONS[config.downsample_method], stream),
-            'emph_segment_reduce')
-        for i, name in enumerate(decoder):
-            self._conv(self._forward_packs[name],
-                       self._parameter(f'{name}.bias'), d[i], d[i + 1], ld_w,
-                       channels, 'relu', word_tiles, WORD_TILE)
-        runtime.check(lib.emph_output_layer(
-            d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
-            self._parameter('output_layer.bias'), channels, 3,
-            table.data_ptr(), word_segment.data_ptr(), ld_w,
-            runtime.AXIS_WORDS, 0, buffers['logits'].data_ptr(), None, stream),
-            'emph_output_layer')
-        return buffers
+        runtime.check(self.lib.emph_gather_columns(
+            batch.features.data_ptr(), batch.plan.ld_frames,
+            gathered.data_ptr(), piece_plan.ld_frames,
+            self.config.num_features, pieces['gather'].data_ptr(),
+            len(piece_plan), runtime.stream()), 'emph_gather_columns')
+        return buffers, Batch(piece_plan, pieces, gathered, None)
 
-    def _forward_backward(self, batch):
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        ld_w = plan.ld_words
-        buffers = self._forward(batch, training=True)
-        view = buffers['view']
+    def _reduce(self, view, batch, buffers):
+        """Every piece pooled over its PADDED axis into its word's column."""
+        pieces = view.meta
+        self._segment_reduce(
+            buffers['frames'][self.config.layers], view.plan.ld_frames,
+            pieces['piece_bounds'], pieces['table'], pieces['word_piece'],
+            buffers['words'][0], batch.plan.ld_words)
+
+    def _reduce_backward(self, view, batch, buffers, dword):
+        """The pooled words back to the columns of their pieces."""
         ld_p = view.plan.ld_frames
-        stream = runtime.stream()
-        piece_tiles = view.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
-        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
-        word_grad_tiles = meta[('tiles', runtime.AXIS_WORDS, GRAD_TILE)]
-        word_segment = meta['word_segment']
-        decoder = [f'word_decoder.{2 * i}' for i in range(layers)]
-        h, d = buffers['frames'], buffers['words']
-        logits, dlogit = buffers['logits'], buffers['dlogit']
-
-        # ---- loss (train/core.py:315-353) and the word-rate backward
-        runtime.check(lib.emph_loss_grad(
-            logits.data_ptr(), batch.targets.data_ptr(),
-            word_segment.data_ptr(), ld_w, plan.total_words,
-            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
-            dlogit.data_ptr(), stream), 'emph_loss_grad')
-        dd, dh = buffers['word_grad'], buffers['frame_grad']
-        runtime.check(lib.emph_output_layer_backward(
-            dlogit.data_ptr(), d[layers].data_ptr(), ld_w,
-            self._parameter('output_layer.weight'), word_segment.data_ptr(),
-            channels, 3, ld_w, self._gradient('output_layer.weight'),
-            self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
-            stream), 'emph_output_layer_backward')
-        dword = self._backward_stack(
-            batch, buffers, decoder, d, dd, ld_w, word_grad_tiles, word_tiles,
-            WORD_TILE)
-        # ---- the pooled words back to the columns of their pieces
-        runtime.check(lib.emph_piece_pool_backward(
-            dword.data_ptr(), ld_w, view.meta['gather'].data_ptr(),
+        tiles = view.meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
+        runtime.check(self.lib.emph_piece_pool_backward(
+            dword.data_ptr(), batch.plan.ld_words,
+            view.meta['gather'].data_ptr(),
             view.meta['piece_column'].data_ptr(), len(view.plan),
-            h[layers].data_ptr(), ld_p, d[0].data_ptr(), dh[0].data_ptr(),
-            ld_p, channels, piece_tiles.data_ptr(),
-            piece_tiles.numel() // runtime.TILE_FIELDS,
-            runtime.REDUCTIONS[config.downsample_method], stream),
-            'emph_piece_pool_backward')
-        self._encoder_backward(view, buffers)
+            buffers['frames'][self.config.layers].data_ptr(), ld_p,
+            buffers['words'][0].data_ptr(),
+            buffers['frame_grad'][0].data_ptr(), ld_p, self.config.channels,
+            tiles.data_ptr(), _tile_count(tiles),
+            runtime.REDUCTIONS[self.config.downsample_method],
+            runtime.stream()), 'emph_piece_pool_backward')
 
 
-class GridTrainer(_Step):
+class GridTrainer(_DecoderStep):
     """`Trainer` for the reference's hyperparameter grid at
     downsample_location 'intermediate' (`check_grid_supported`): every
     activation, reduction, channel count and kernel size of
@@ -1331,246 +1326,59 @@ class GridTrainer(_Step):
     (`emph_activation_dropout_gradient`)."""
 
     _check = staticmethod(check_grid_supported)
+    _weight_grad_kernel = 'emph_conv_weight_grad_any'
+    _output_layer_backward = 'emph_output_layer_backward_any'
 
     def __init__(self, config=None, checkpoint=None, gpu=None, lr=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, seed=0, precision='f32'):
         check_grid_precision(precision)
         super().__init__(config, checkpoint, gpu, lr, betas, eps, seed,
                          precision)
-        self._keeps_pre = self.config.activation in ('gelu', 'silu')
 
-    def _layer_shape(self, name):
-        """(c_in, kernel size) of conv layer `name`."""
-        _, shape = self.offsets[f'{name}.weight']
-        return shape[1], shape[2]
-
-    def _buffers(self, plan):
-        """The activations and gradients of a step for a packed layout, kept
-        between steps (zero at first, so that padding columns stay finite)."""
+    def _workspace_needs(self, frame_tiles, word_tiles):
         config = self.config
-        frame_tiles = len(plan.tiles(runtime.AXIS_FRAMES, GRAD_TILE))
-        word_tiles = len(plan.tiles(runtime.AXIS_WORDS, GRAD_TILE))
-        channels, layers = config.channels, config.layers
+        channels = config.channels
         shapes = [(config.num_features, config.encoder_kernel_size, frame_tiles)]
-        if layers:
+        if config.layers:
             shapes += [(channels, config.encoder_kernel_size, frame_tiles),
                        (channels, config.decoder_kernel_size, word_tiles)]
-        workspace = max(
+        return {'workspace': max(
             int(self.lib.emph_conv_weight_grad_any_workspace(
                 c_in, channels, kernel_size, tiles))
-            for c_in, kernel_size, tiles in shapes)
-        key = (plan.ld_frames, plan.ld_words, workspace)
-        found = self._workspace.get(key)
-        if found is None:
-            self._workspace.clear()
-            zeros = lambda *shape: torch.zeros(  # noqa: E731
-                shape, dtype=torch.float32, device=self.device)
-            found = {
-                'frames': zeros(layers + 1, channels, plan.ld_frames),
-                'words': zeros(layers + 1, channels, plan.ld_words),
-                'frame_grad': zeros(2, channels, plan.ld_frames),
-                'word_grad': zeros(2, channels, plan.ld_words),
-                'logits': zeros(plan.ld_words),
-                'dlogit': zeros(plan.ld_words),
-                'slabs': zeros(max(workspace, 1))}
-            if self._keeps_pre:
-                found['pre_frames'] = zeros(layers, channels, plan.ld_frames)
-                found['pre_words'] = zeros(layers, channels, plan.ld_words)
-            self._workspace[key] = found
-        return found
+            for c_in, kernel_size, tiles in shapes)}
 
-    def _grid_conv(self, pack, bias, x, y, ld, c_in, kernel_size, activation,
-                   tiles, tile):
-        runtime.check(self.lib.emph_conv1d(
-            x.data_ptr(), ld, y.data_ptr(), ld,
-            self.packs.data_ptr() + 4 * pack[0], bias, c_in,
-            self.config.channels, kernel_size,
-            runtime.ACTIVATIONS[activation], tiles.data_ptr(),
-            tiles.numel() // runtime.TILE_FIELDS, tile, 0, runtime.stream()),
-            'emph_conv1d')
+    def _slab_floats(self, needs):
+        return max(needs['workspace'], 1)
 
-    def _forward_stack(self, names, outputs, pre, ld, tiles, tile, training):
-        """A conv stack (`model/layers/convolution.py:22-37`): outputs[i + 1]
-        = dropout(act(conv(outputs[i]))), every output kept, and the
-        pre-activation too where the activation's derivative reads it."""
-        activation = self.config.activation
-        drop = training and self.dropout > 0.
-        for i, name in enumerate(names):
-            c_in, kernel_size = self._layer_shape(name)
-            bias = self._parameter(f'{name}.bias')
-            pack = self._forward_packs[name]
-            if training and self._keeps_pre:
-                self._grid_conv(pack, bias, outputs[i], pre[i], ld, c_in,
-                                kernel_size, None, tiles, tile)
-                runtime.check(self.lib.emph_activation_dropout(
-                    pre[i].data_ptr(), outputs[i + 1].data_ptr(),
-                    pre[i].numel(), runtime.ACTIVATIONS[activation],
-                    self.dropout if drop else 0., self.seed & (1 << 64) - 1,
-                    dropout_module.stream_of(self.config, name), self.steps,
-                    runtime.stream()), 'emph_activation_dropout')
-                continue
-            self._grid_conv(pack, bias, outputs[i], outputs[i + 1], ld, c_in,
-                            kernel_size, activation, tiles, tile)
-            if drop:
-                self._dropout(name, outputs[i + 1])
+    def _buffer_shapes(self, ld_frames, ld_words, needs):
+        """... and the pre-activations, where the activation's derivative
+        reads them."""
+        shapes = super()._buffer_shapes(ld_frames, ld_words, needs)
+        if self.config.activation in ('gelu', 'silu'):
+            channels, layers = self.config.channels, self.config.layers
+            shapes['pre_frames'] = (layers, channels, ld_frames)
+            shapes['pre_words'] = (layers, channels, ld_words)
+        return shapes
 
-    def _forward(self, batch, training=False):
-        """The forward launches of a step; returns the step's buffers, whose
-        'logits' then hold the packed logits [ld_words].  `training`: the
-        train-mode forward, which keeps what the backward reads and applies
-        the dropout masks of the step; without it the eval model, whose GELU
-        and SiLU run in the convolution's epilogue (the same function, the
-        same bits)."""
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        ld_f, ld_w = plan.ld_frames, plan.ld_words
-        buffers = self._buffers(plan)
-        stream = runtime.stream()
-        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
-        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
-        table, word_segment = meta['table'], meta['word_segment']
-        h, d = buffers['frames'], buffers['words']
-
-        self._grid_conv(
-            self._forward_packs['input_layer'],
-            self._parameter('input_layer.bias'), batch.features, h[0], ld_f,
-            config.num_features, config.encoder_kernel_size, None,
-            frame_tiles, FRAME_TILE)
-        self._forward_stack(
-            [f'frame_encoder.{2 * i}' for i in range(layers)], h,
-            buffers.get('pre_frames'), ld_f, frame_tiles, FRAME_TILE, training)
-        runtime.check(lib.emph_segment_reduce(
-            h[layers].data_ptr(), ld_f, meta['bounds'].data_ptr(),
-            d[0].data_ptr(), ld_w, channels, table.data_ptr(),
-            word_segment.data_ptr(), ld_w,
-            runtime.REDUCTIONS[config.downsample_method], stream),
-            'emph_segment_reduce')
-        self._forward_stack(
-            [f'word_decoder.{2 * i}' for i in range(layers)], d,
-            buffers.get('pre_words'), ld_w, word_tiles, WORD_TILE, training)
-        runtime.check(lib.emph_output_layer(
-            d[layers].data_ptr(), ld_w, self._parameter('output_layer.weight'),
-            self._parameter('output_layer.bias'), channels,
-            config.decoder_kernel_size, table.data_ptr(),
-            word_segment.data_ptr(), ld_w, runtime.AXIS_WORDS, 0,
-            buffers['logits'].data_ptr(), None, stream), 'emph_output_layer')
-        return buffers
-
-    def _grid_weight_grad(self, dy, x, ld, name, tiles, buffers):
-        c_in, kernel_size = self._layer_shape(name)
-        runtime.check(self.lib.emph_conv_weight_grad_any(
-            dy.data_ptr(), ld, x.data_ptr(), ld, c_in, self.config.channels,
-            kernel_size, tiles.data_ptr(),
-            tiles.numel() // runtime.TILE_FIELDS, GRAD_TILE,
-            buffers['slabs'].data_ptr(), self._gradient(f'{name}.weight'),
-            self._gradient(f'{name}.bias'), runtime.stream()),
-            'emph_conv_weight_grad_any')
-
-    def _grid_backward_stack(self, buffers, names, outputs, pre, gradient, ld,
-                             grad_tiles, tiles, tile):
-        """Backward of a conv stack, from the gradient of the last output
-        (gradient[0]) down to the gradient of outputs[0]; returns the buffer
-        that holds it."""
-        lib, config, stream = self.lib, self.config, runtime.stream()
-        activation = runtime.ACTIVATIONS[config.activation]
-        current = 0
-        for i in range(len(names) - 1, -1, -1):
-            name = names[i]
-            dy = gradient[current]
-            source = pre[i] if self._keeps_pre else outputs[i + 1]
-            if self.dropout > 0.:
-                runtime.check(lib.emph_activation_dropout_gradient(
-                    source.data_ptr(), dy.data_ptr(), dy.numel(), activation,
-                    self.dropout, self.seed & (1 << 64) - 1,
-                    dropout_module.stream_of(config, name), self.steps,
-                    stream), 'emph_activation_dropout_gradient')
-            else:
-                runtime.check(lib.emph_activation_gradient(
-                    source.data_ptr(), dy.data_ptr(), dy.numel(), activation,
-                    stream), 'emph_activation_gradient')
-            self._grid_weight_grad(dy, outputs[i], ld, name, grad_tiles,
-                                   buffers)
-            _, kernel_size = self._layer_shape(name)
-            self._grid_conv(self._backward_packs[name], None, dy,
-                            gradient[1 - current], ld, config.channels,
-                            kernel_size, None, tiles, tile)
-            current = 1 - current
-        return gradient[current]
-
-    def _forward_backward(self, batch):
-        config, lib, plan, meta = self.config, self.lib, batch.plan, batch.meta
-        channels, layers = config.channels, config.layers
-        ld_f, ld_w = plan.ld_frames, plan.ld_words
-        buffers = self._forward(batch, training=True)
-        stream = runtime.stream()
-        frame_tiles = meta[('tiles', runtime.AXIS_FRAMES, FRAME_TILE)]
-        word_tiles = meta[('tiles', runtime.AXIS_WORDS, WORD_TILE)]
-        word_grad_tiles = meta[('tiles', runtime.AXIS_WORDS, GRAD_TILE)]
-        table, bounds = meta['table'], meta['bounds']
-        word_segment = meta['word_segment']
-        h, d = buffers['frames'], buffers['words']
-        dh, dd = buffers['frame_grad'], buffers['word_grad']
-        logits, dlogit = buffers['logits'], buffers['dlogit']
-
-        # ---- loss (train/core.py:315-353) and the word-rate backward
-        runtime.check(lib.emph_loss_grad(
-            logits.data_ptr(), batch.targets.data_ptr(),
-            word_segment.data_ptr(), ld_w, plan.total_words,
-            runtime.BCE_FORMS[config.loss], self.loss.data_ptr(),
-            dlogit.data_ptr(), stream), 'emph_loss_grad')
-        runtime.check(lib.emph_output_layer_backward_any(
-            dlogit.data_ptr(), d[layers].data_ptr(), ld_w,
-            self._parameter('output_layer.weight'), word_segment.data_ptr(),
-            channels, config.decoder_kernel_size, ld_w,
-            self._gradient('output_layer.weight'),
-            self._gradient('output_layer.bias'), dd[0].data_ptr(), ld_w,
-            stream), 'emph_output_layer_backward_any')
-        dword = self._grid_backward_stack(
-            buffers, [f'word_decoder.{2 * i}' for i in range(layers)], d,
-            buffers.get('pre_words'), dd, ld_w, word_grad_tiles, word_tiles,
-            WORD_TILE)
-        # ---- the reduce (max reads the encoder's output and the pooled
-        # words, both kept), the frame encoder and the input layer
-        runtime.check(lib.emph_segment_reduce_backward(
-            dword.data_ptr(), ld_w, bounds.data_ptr(), h[layers].data_ptr(),
-            ld_f, d[0].data_ptr(), dh[0].data_ptr(), ld_f, channels,
-            table.data_ptr(), frame_tiles.data_ptr(),
-            frame_tiles.numel() // runtime.TILE_FIELDS,
-            runtime.REDUCTIONS[config.downsample_method], stream),
-            'emph_segment_reduce_backward')
-        dinput = self._grid_backward_stack(
-            buffers, [f'frame_encoder.{2 * i}' for i in range(layers)], h,
-            buffers.get('pre_frames'), dh, ld_f, frame_tiles, frame_tiles,
-            FRAME_TILE)
-        self._grid_weight_grad(dinput, batch.features, ld_f, 'input_layer',
-                               frame_tiles, buffers)
-
-
-def _select(config, precision):
-    """The class of the step that trains `config`, every check made and
-    nothing constructed: the specialised step of the configuration's location
-    (what `trainer_for` builds) first, `GridTrainer` where that refuses and
-    `check_grid_supported` passes, otherwise the specialised step's refusal."""
-    location = config.downsample_location
-    if location == 'input':
-        check, name = check_pieces_supported, 'PieceTrainer'
-    elif location in ('inference', 'loss'):
-        check, name = check_encoder_supported, 'EncoderTrainer'
-    else:
-        check, name = check_supported, 'Trainer'
-    try:
-        check(config)
-    except NotImplementedError:
-        try:
-            check_grid_supported(config)
-        except NotImplementedError:
-            pass
+    def _activation_backward(self, name, y, pre, dy):
+        """Off the pre-activation where it is kept, off the kept output
+        otherwise; under dropout with the regenerated mask."""
+        source = y if pre is None else pre
+        activation = runtime.ACTIVATIONS[self.config.activation]
+        if self.dropout > 0.:
+            runtime.check(self.lib.emph_activation_dropout_gradient(
+                source.data_ptr(), dy.data_ptr(), dy.numel(), activation,
+                self.dropout, *self._mask(name), runtime.stream()),
+                'emph_activation_dropout_gradient')
         else:
-            check_grid_precision(precision)
-            return globals()['GridTrainer']
-        raise
-    check_precision(precision)
-    return globals()[name]
+            runtime.check(self.lib.emph_activation_gradient(
+                source.data_ptr(), dy.data_ptr(), dy.numel(), activation,
+                runtime.stream()), 'emph_activation_gradient')
+
+
+def _build(config, arguments, **dispatch):
+    config = config or api.active_config()
+    return step_class(config, **dispatch)(config, **arguments)
 
 
 def select_trainer(config=None, **arguments):
@@ -1579,22 +1387,23 @@ def select_trainer(config=None, **arguments):
     its bits), a `GridTrainer` where none does and `check_grid_supported`
     passes; otherwise the specialised step's refusal.  Every check comes
     before anything is constructed or a GPU is needed."""
-    config = config or api.active_config()
-    return _select(config, arguments.get('precision', 'f32'))(
-        config, **arguments)
+    return _build(config, arguments,
+                  precision=arguments.get('precision', 'f32'))
+
+
+MADE_LOCATIONS = ('intermediate', 'inference', 'loss')
 
 
 def trainer_for(config=None, **arguments):
-    """The step that trains `config` at any downsample_location: a
-    `PieceTrainer` at 'input' where `check_pieces_supported` passes,
-    `make_trainer(...)` everywhere else; the refusal that names the offending
-    field comes first, before a GPU is needed."""
+    """The step that trains `config` at any downsample_location, never the
+    grid step: a `PieceTrainer` at 'input' where `check_pieces_supported` and
+    `check_precision` pass, `make_trainer(...)` everywhere else; the refusal
+    that names the offending field comes first, before a GPU is needed."""
     config = config or api.active_config()
-    if config.downsample_location == 'input':
-        check_pieces_supported(config)
-        check_precision(arguments.get('precision', 'f32'))
-        return PieceTrainer(config, **arguments)
-    return make_trainer(config, **arguments)
+    if config.downsample_location in MADE_LOCATIONS:
+        return make_trainer(config, **arguments)
+    return _build(config, arguments, grid=False,
+                  precision=arguments.get('precision', 'f32'))
 
 
 def make_trainer(config=None, **arguments):
@@ -1602,9 +1411,4 @@ def make_trainer(config=None, **arguments):
     passes, an `EncoderTrainer` at downsample_location 'inference' and 'loss'
     where `check_encoder_supported` passes; otherwise the refusal that names
     the offending field, before a GPU is needed."""
-    config = config or api.active_config()
-    if config.downsample_location in ('inference', 'loss'):
-        check_encoder_supported(config)
-        return EncoderTrainer(config, **arguments)
-    check_supported(config)
-    return Trainer(config, **arguments)
+    return _build(config, arguments, grid=False, locations=MADE_LOCATIONS)

@@ -109,7 +109,7 @@ def train(dataset, directory, gpu=None, *, partition_dir,
     Returns the final checkpoint's path."""
     from .. import data
     config = config or api.active_config()
-    core._select(config, precision)                 # before any file is read
+    core.step_class(config, precision)              # before any file is read
     directory = os.fspath(directory)
     os.makedirs(directory, exist_ok=True)
 
