@@ -10,6 +10,9 @@ prefix sums, so that a caller of the reference's ATen ops
     torch.ops.emphases_amd.encoder_layer(x, in_w, in_b, out_w, out_b, norm1_w, norm1_b,
                                          ff1_w, ff1_b, ff2_w, ff2_b, norm2_w, norm2_b,
                                          cu_T, heads)                  transformer.py:18-30
+    torch.ops.emphases_amd.encoder_layer_dropout(x, <the same twelve>, cu_T, heads,
+                                         p, seed, stream_base, step)   the same in .train()
+    torch.ops.emphases_amd.dropout(x, p, seed, stream, step)           transformer.py:51-52
     torch.ops.emphases_amd.prominence_forward(audio_packed, cu_samples, bounds, cu_words)
                                                                        core.py:295-342
 
@@ -29,7 +32,9 @@ Autograd.  `conv1d_same_act` (gradients of `x`, `weight`, `bias`) and
 the way to a second backward, raises) and carry a
 `register_fake` shape rule; so is `encoder_layer` (gradients of `x` and of
 all twelve parameters; 80 channels in 2 heads, its dropouts the identity:
-see its docstring) and `logmel` (gradient of a float `audio_packed`: the
+see its docstring; `encoder_layer_dropout` is the same layer in training mode
+under the reference's four dropouts as specified masks, and `dropout` the
+mask alone) and `logmel` (gradient of a float `audio_packed`: the
 waveform end of the chain, so d(prominence)/d(audio) exists on the seams; no
 `register_fake` - its shape depends on the values of `cu_samples`);
 `prominence_forward` alone stays non-differentiable.  The backward runs on
@@ -77,7 +82,7 @@ from . import runtime
 from . import weights as weights_module
 
 __all__ = ['logmel', 'conv1d_same_act', 'segment_reduce', 'encoder_layer',
-           'prominence_forward']
+           'encoder_layer_dropout', 'dropout', 'prominence_forward']
 
 GRAD_TILE = 64       # emph_conv_weight_grad_any, emph_segment_reduce_backward
 DIRECT_TILE = 64     # emph_conv1d of the device-packed path and of the data gradient
@@ -754,13 +759,20 @@ class _LayerRun:
     and V by `emph_conv1d` k = 1, `emph_attention`, out_proj,
     `emph_add_layernorm`, linear1 + ReLU, linear2, `emph_add_layernorm`.  The
     weights are packed on the device (`_device_pack`): nothing is copied to
-    the host."""
+    the host.
 
-    def __init__(self, x, tensors, heads, layout, index):
+    `dropout` = (p, seed, stream_base, step) draws the reference's four
+    dropouts of the layer (`train/dropout.py`): `emph_attention_dropout` in
+    place of `emph_attention` under stream_base, and `emph_dropout` in place
+    on `projected`, `hidden` and `fed` (whole packed buffers [rows, ld]) under
+    stream_base + 1, + 2, + 3."""
+
+    def __init__(self, x, tensors, heads, layout, index, dropout=None):
         (self.in_w, self.in_b, self.out_w, self.out_b, self.norm1_w,
          self.norm1_b, self.ff1_w, self.ff1_b, self.ff2_w, self.ff2_b,
          self.norm2_w, self.norm2_b) = tensors
         self.layout, self.index, self.heads = layout, index, int(heads)
+        self.dropout = dropout
         self.ld = ld = layout.plan.ld_frames
         self.channels = channels = int(x.shape[0])
         self.device = x.device
@@ -778,13 +790,23 @@ class _LayerRun:
                   self.pack(self.in_w, (2 * channels, 3 * channels)),
                   bias + 4 * 2 * channels, channels, channels, transpose=True)
         self.attended = self.zeros(channels)
-        runtime.check(self.lib.emph_attention(
-            self.qk.data_ptr(), self.v.data_ptr(), self.attended.data_ptr(),
-            ld, channels, self.heads, self.tiles.data_ptr(), self.n_tiles,
-            DIRECT_TILE, None, runtime.stream()), 'emph_attention')
+        if dropout is None:
+            runtime.check(self.lib.emph_attention(
+                self.qk.data_ptr(), self.v.data_ptr(),
+                self.attended.data_ptr(), ld, channels, self.heads,
+                self.tiles.data_ptr(), self.n_tiles, DIRECT_TILE, None,
+                runtime.stream()), 'emph_attention')
+        else:
+            p, seed, base, step = dropout
+            runtime.check(self.lib.emph_attention_dropout(
+                self.qk.data_ptr(), self.v.data_ptr(),
+                self.attended.data_ptr(), ld, channels, self.heads,
+                self.tiles.data_ptr(), self.n_tiles, GRAD_TILE, p, seed, base,
+                step, runtime.stream()), 'emph_attention_dropout')
         self.projected = self.zeros(channels)
         self.conv(self.attended, self.projected, self.pack(self.out_w),
                   _float_pointer(self.out_b, self.keep), channels, channels)
+        self.drop(self.projected, 1)
         self.normed1 = self.zeros(channels)
         self.add_layernorm(self.x, self.projected, self.normed1, self.norm1_w,
                            self.norm1_b)
@@ -793,9 +815,11 @@ class _LayerRun:
         self.conv(self.normed1, self.hidden, self.pack(self.ff1_w),
                   _float_pointer(self.ff1_b, self.keep), channels, hidden,
                   activation='relu')
+        self.drop(self.hidden, 2)
         self.fed = self.zeros(channels)
         self.conv(self.hidden, self.fed, self.pack(self.ff2_w),
                   _float_pointer(self.ff2_b, self.keep), hidden, channels)
+        self.drop(self.fed, 3)
         self.normed2 = self.zeros(channels)
         self.add_layernorm(self.normed1, self.fed, self.normed2, self.norm2_w,
                            self.norm2_b)
@@ -806,6 +830,16 @@ class _LayerRun:
 
     def pack(self, weight, rows=None, flipped=False):
         return _device_pack(weight, self.index, flipped, rows)
+
+    def drop(self, buffer, site):
+        """The mask of stream_base + `site` on a packed buffer or on its
+        gradient, in place (nothing without `dropout`)."""
+        if self.dropout is None:
+            return
+        p, seed, base, step = self.dropout
+        runtime.check(self.lib.emph_dropout(
+            buffer.data_ptr(), buffer.numel(), 0, p, seed, base + site, step,
+            runtime.stream()), 'emph_dropout')
 
     def conv(self, x, y, pack, bias, c_in, c_out, activation=None,
              transpose=False):
@@ -882,16 +916,23 @@ class _LayerRun:
         dy = self.layout.scatter(grad, self.layout.frame_columns, ld)
         ds2, dgamma, dbeta = self.layernorm_backward(
             self.normed1 + self.fed, self.norm2_w, dy)
+        dfed = ds2
+        if self.dropout is not None:
+            dfed = ds2.clone()
+            self.drop(dfed, 3)
         out[11], out[12] = (dgamma if need[11] else None,
                             dbeta if need[12] else None)
         if not any(need[:11]):
             return out
-        linear_grads(ds2, self.hidden, self.ff2_w, 9)
+        linear_grads(dfed, self.hidden, self.ff2_w, 9)
         if not any(need[:9]):
             return out
         dhidden = self.zeros(hidden)
-        self.conv(ds2, dhidden, self.pack(self.ff2_w, flipped=True), None,
+        self.conv(dfed, dhidden, self.pack(self.ff2_w, flipped=True), None,
                   channels, hidden)
+        # (the kept `hidden` is positive only where the ReLU passed AND the
+        # mask kept: the activation gradient below selects by either)
+        self.drop(dhidden, 2)
         runtime.check(self.lib.emph_activation_gradient(
             self.hidden.data_ptr(), dhidden.data_ptr(), dhidden.numel(),
             runtime.ACTIVATIONS['relu'], runtime.stream()),
@@ -907,21 +948,39 @@ class _LayerRun:
             self.x + self.projected, self.norm1_w, dnormed1)
         out[5], out[6] = (dgamma if need[5] else None,
                           dbeta if need[6] else None)
-        linear_grads(ds1, self.attended, self.out_w, 3)
+        dprojected = ds1
+        if self.dropout is not None:
+            dprojected = ds1.clone()
+            self.drop(dprojected, 1)
+        linear_grads(dprojected, self.attended, self.out_w, 3)
         if not any(need[:3]):
             return out
         dattended = self.zeros(channels)
-        self.conv(ds1, dattended, self.pack(self.out_w, flipped=True), None,
-                  channels, channels)
+        self.conv(dprojected, dattended, self.pack(self.out_w, flipped=True),
+                  None, channels, channels)
         dqkv = self.zeros(3 * channels)
-        workspace = torch.empty(
-            max(1, int(self.lib.emph_attention_backward_workspace(
-                ld, self.heads))), dtype=torch.float32, device=device)
-        runtime.check(self.lib.emph_attention_backward(
-            self.qk.data_ptr(), self.v.data_ptr(), self.attended.data_ptr(),
-            dattended.data_ptr(), dqkv.data_ptr(), ld, channels, self.heads,
-            self.tiles.data_ptr(), self.n_tiles, GRAD_TILE,
-            workspace.data_ptr(), runtime.stream()), 'emph_attention_backward')
+        size = (self.lib.emph_attention_backward_workspace
+                if self.dropout is None else
+                self.lib.emph_attention_dropout_backward_workspace)
+        workspace = torch.empty(max(1, int(size(ld, self.heads))),
+                                dtype=torch.float32, device=device)
+        if self.dropout is None:
+            runtime.check(self.lib.emph_attention_backward(
+                self.qk.data_ptr(), self.v.data_ptr(),
+                self.attended.data_ptr(), dattended.data_ptr(),
+                dqkv.data_ptr(), ld, channels, self.heads,
+                self.tiles.data_ptr(), self.n_tiles, GRAD_TILE,
+                workspace.data_ptr(), runtime.stream()),
+                'emph_attention_backward')
+        else:
+            p, seed, base, step = self.dropout
+            runtime.check(self.lib.emph_attention_dropout_backward(
+                self.qk.data_ptr(), self.v.data_ptr(),
+                self.attended.data_ptr(), dattended.data_ptr(),
+                dqkv.data_ptr(), ld, channels, self.heads,
+                self.tiles.data_ptr(), self.n_tiles, GRAD_TILE,
+                workspace.data_ptr(), p, seed, base, step, runtime.stream()),
+                'emph_attention_dropout_backward')
         linear_grads(dqkv, self.x, self.in_w, 1, rows=channels)
         if need[0]:
             dx = self.zeros(channels)
@@ -946,11 +1005,10 @@ def encoder_layer(x: torch.Tensor, in_proj_weight: torch.Tensor,
     (attention within a segment only): x `[C, sum T_i]` -> `[C, sum T_i]`; no
     positional encoding is added.
 
-    DROPOUT IS THE IDENTITY, in the forward and in the backward: the
-    reference's layer TRAINS with its internal dropout of 0.1 (attention
-    weights, both residual branches, the feed-forward), which this op does not
-    draw - a deliberate deviation (dropout inside the attention kernel is not
-    built).
+    DROPOUT IS THE IDENTITY, in the forward and in the backward: this op is
+    the layer in `.eval()`.  The reference's layer TRAINS with its internal
+    dropout of 0.1 (attention weights, both residual branches, the
+    feed-forward); `encoder_layer_dropout` draws those, as specified masks.
 
     A parameter set that has never changed since the op first saw it runs on
     the fused inference engine of the layer (its packs made once on the host);
@@ -1036,6 +1094,150 @@ def _layer_backward(ctx, grad):
 
 
 encoder_layer.register_autograd(_layer_backward, setup_context=_layer_setup)
+
+
+def _check_layer_shape(name, channels, heads):
+    if channels != LAYER_CHANNELS:
+        raise NotImplementedError(
+            f'{name} supports x of {LAYER_CHANNELS} channels only, not '
+            f'{channels}')
+    if heads != LAYER_HEADS:
+        raise NotImplementedError(
+            f'{name} supports heads={LAYER_HEADS} only, not heads={heads}')
+
+
+def _mask_arguments(p, seed, stream, step):
+    """(float32 p, seed mod 2^64, stream, step) as the C ABI carries them."""
+    p = float(np.float32(p))
+    if not 0. <= p < 1.:
+        raise ValueError(f'p = {p} (0 <= p < 1)')
+    if not (0 <= stream < 1 << 32 and 0 <= step < 1 << 32):
+        raise ValueError('stream and step are unsigned 32-bit')
+    return p, int(seed) & (1 << 64) - 1, int(stream), int(step)
+
+
+@torch.library.custom_op('emphases_amd::encoder_layer_dropout', mutates_args=())
+def encoder_layer_dropout(
+        x: torch.Tensor, in_proj_weight: torch.Tensor,
+        in_proj_bias: torch.Tensor, out_proj_weight: torch.Tensor,
+        out_proj_bias: torch.Tensor, norm1_weight: torch.Tensor,
+        norm1_bias: torch.Tensor, linear1_weight: torch.Tensor,
+        linear1_bias: torch.Tensor, linear2_weight: torch.Tensor,
+        linear2_bias: torch.Tensor, norm2_weight: torch.Tensor,
+        norm2_bias: torch.Tensor, cu_T: torch.Tensor, heads: int, p: float,
+        seed: int, stream_base: int, step: int) -> torch.Tensor:
+    """`encoder_layer` in TRAINING mode: the four dropouts of
+    `nn.TransformerEncoderLayer` (the attention weights after the softmax,
+    `dropout1` on the attention branch, `dropout` on the hidden layer after
+    its ReLU, `dropout2` on the feed-forward branch), each with probability
+    `p`, drawn as `train/dropout.py` specifies from (`seed`, `stream_base`
+    + 0 .. 3, `step`): a pure function of its arguments.  The element-wise
+    masks index the layer's packed buffer [rows, ld] of the frame plan of
+    `cu_T`; the attention mask is `attention_keep_mask`.
+
+    Always the unfused sequence of `_LayerRun` (`emph_attention_dropout`,
+    `emph_dropout`).  Backward (once): recomputed with the same four
+    integers, walked back through `emph_attention_dropout_backward` and the
+    same masks on the gradients.  80 channels in 2 heads only."""
+    _check_layer_shape('encoder_layer_dropout', int(x.shape[0]), int(heads))
+    dropout = _mask_arguments(p, seed, stream_base, step)
+    index = _device_index(x)
+    counts, _ = _counts(cu_T)
+    if int(counts.sum()) != x.shape[1]:
+        raise ValueError('cu_T does not cover the columns of x')
+    tensors = (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias,
+               norm1_weight, norm1_bias, linear1_weight, linear1_bias,
+               linear2_weight, linear2_bias, norm2_weight, norm2_bias)
+    layout = _layout(x.device, counts)
+    with torch.cuda.device(index):
+        run = _LayerRun(x, tensors, heads, layout, index, dropout)
+        return run.normed2.index_select(1, layout.frame_columns)
+
+
+@encoder_layer_dropout.register_fake
+def _encoder_layer_dropout_fake(
+        x, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias,
+        norm1_weight, norm1_bias, linear1_weight, linear1_bias, linear2_weight,
+        linear2_bias, norm2_weight, norm2_bias, cu_T, heads, p, seed,
+        stream_base, step):
+    return x.new_empty(x.shape, dtype=torch.float32)
+
+
+def _layer_dropout_setup(ctx, inputs, output):
+    ctx.heads = inputs[14]
+    ctx.dropout = tuple(inputs[15:19])
+    ctx.save_for_backward(*inputs[:14])
+
+
+def _layer_dropout_backward(ctx, grad):
+    _once('encoder_layer_dropout')
+    saved = ctx.saved_tensors
+    x, tensors, cu_T = saved[0], saved[1:13], saved[13]
+    need = list(ctx.needs_input_grad[:13])
+    if not any(need):
+        return (None,) * 19
+    index = _device_index(grad)
+    counts, _ = _counts(cu_T)
+    layout = _layout(x.device, counts)
+    with torch.cuda.device(index):
+        run = _LayerRun(x.detach(), tensors, ctx.heads, layout, index,
+                        _mask_arguments(*ctx.dropout))
+        grads = run.backward(grad, need)
+        if grads[0] is not None:
+            grads[0] = grads[0].index_select(1, layout.frame_columns)
+    grads = [None if g is None else g.to(source.dtype).reshape(source.shape)
+             for g, source in zip(grads, saved[:13])]
+    return (*grads, None, None, None, None, None, None)
+
+
+encoder_layer_dropout.register_autograd(
+    _layer_dropout_backward, setup_context=_layer_dropout_setup)
+
+
+def _masked(x, p, seed, stream, step):
+    p, seed, stream, step = _mask_arguments(p, seed, stream, step)
+    if x.dtype != torch.float32:
+        raise TypeError(f'dropout takes float32, not {x.dtype}')
+    index = _device_index(x)
+    count = x.numel()
+    if not count:
+        return x.clone()
+    # (emph_dropout works in whole quads: the tail is padded)
+    out = torch.zeros((count + 3) // 4 * 4, dtype=torch.float32,
+                      device=x.device)
+    out[:count] = x.reshape(-1)
+    with torch.cuda.device(index):
+        runtime.check(runtime.library().emph_dropout(
+            out.data_ptr(), out.numel(), 0, p, seed, stream, step,
+            runtime.stream()), 'emph_dropout')
+    return out[:count].reshape(x.shape).clone()
+
+
+@torch.library.custom_op('emphases_amd::dropout', mutates_args=())
+def dropout(x: torch.Tensor, p: float, seed: int, stream: int,
+            step: int) -> torch.Tensor:
+    """The specified mask (`train/dropout.py`, `keep_mask`) on the flat index
+    of a float32 tensor: a copy through `emph_dropout`, kept elements scaled
+    by float32(1 / (1 - p)).  Differentiable: the same mask on the gradient.
+    The positional site of `TransformerModel(reference_dropout=True)`."""
+    return _masked(x, p, seed, stream, step)
+
+
+@dropout.register_fake
+def _dropout_fake(x, p, seed, stream, step):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+def _dropout_setup(ctx, inputs, output):
+    ctx.mask = tuple(inputs[1:5])
+
+
+def _dropout_backward(ctx, grad):
+    _once('dropout')
+    return _masked(grad.to(torch.float32), *ctx.mask), None, None, None, None
+
+
+dropout.register_autograd(_dropout_backward, setup_context=_dropout_setup)
 
 
 @torch.library.custom_op('emphases_amd::prominence_forward', mutates_args=())

@@ -268,6 +268,13 @@ SIGNATURES = {
     'emph_attention_backward': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i32, _i32, _ptr, _i32, _i32, _ptr,
         _ptr]),
+    'emph_attention_dropout': (_c.c_int, [
+        _ptr, _ptr, _ptr, _i64, _i32, _i32, _ptr, _i32, _i32, _f32,
+        _c.c_uint64, _c.c_uint32, _c.c_uint32, _ptr]),
+    'emph_attention_dropout_backward_workspace': (_i64, [_i64, _i32]),
+    'emph_attention_dropout_backward': (_c.c_int, [
+        _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i32, _i32, _ptr, _i32, _i32, _ptr,
+        _f32, _c.c_uint64, _c.c_uint32, _c.c_uint32, _ptr]),
     'emph_add_layernorm_backward_parts': (_i32, [_i32]),
     'emph_add_layernorm_backward': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _i64, _i32, _f32, _ptr, _i32, _i32, _ptr, _ptr,

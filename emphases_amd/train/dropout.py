@@ -19,6 +19,10 @@ step can be repeated, resumed and checked bit for bit.  `emph_dropout`
   `scale(p)`.  The probability is what the C ABI carries, float32(p): both
   are functions of that value alone, so that the library and this file agree
   for every p.
+* The Transformer's five dropouts (`TransformerModel(reference_dropout=True)`,
+  `emph_attention_dropout` in `csrc/transformer_grad.hip`): the streams of
+  `transformer_stream`, `keep_mask` for the element-wise sites and
+  `attention_keep_mask` for the softmax weights, at the end of this file.
 """
 import numpy as np
 
@@ -83,3 +87,71 @@ def keep_mask(seed, stream, step, count, p, origin=0):
     words = np.stack(np.broadcast_arrays(*words), axis=1).ravel()
     skip = origin - 4 * first
     return words[skip:skip + count] >= np.uint32(threshold(p))
+
+
+# ---- the Transformer (`TransformerModel(reference_dropout=True)`)
+#
+# The reference's Transformer hard-codes its dropouts; they are constants of
+# the architecture, not of the configuration (`Config.dropout` is the conv
+# stacks' switch and stays refused for the Transformer).
+
+# model/layers/transformer.py:18-23: `torch.nn.TransformerEncoderLayer(
+# channels, 2, dim_feedforward=CHANNELS)` keeps torch's default dropout=0.1 on
+# the attention weights, on both residual branches and on the hidden layer
+TRANSFORMER_LAYER_DROPOUT = 0.1
+# model/layers/transformer.py:17: `PositionalEncoding(channels, .1)`
+TRANSFORMER_POSITION_DROPOUT = 0.1
+
+TRANSFORMER_STACKS = ('frame_encoder', 'word_decoder')
+# the four masks of a layer, in the order of their stream ids
+TRANSFORMER_SITES = ('attention', 'residual1', 'hidden', 'residual2')
+
+
+def transformer_stream(config, stack, layer=None, site='position'):
+    """The mask stream of one dropout of the Transformer: stack s of
+    `TRANSFORMER_STACKS` owns the ids s (1 + 4 layers) + ..., first its
+    positional site (`layer` None), then four per layer in the order of
+    `TRANSFORMER_SITES`.  `encoder_layer_dropout` takes the id of a layer's
+    'attention' site as its `stream_base`."""
+    first = TRANSFORMER_STACKS.index(stack) * (1 + 4 * config.layers)
+    if layer is None:
+        assert site == 'position'
+        return first
+    assert 0 <= int(layer) < config.layers
+    return first + 1 + 4 * int(layer) + TRANSFORMER_SITES.index(site)
+
+
+def attention_keep_mask(seed, stream, step, p, ld, head, query_column, keys):
+    """bool [keys]: which attention weights of one query are kept.  The query
+    is (head, its column in the packed buffer [., ld]); the keys are counted
+    from the first position of its segment.  Key quad k // 4 has the counter
+    (k // 4, head ld + query_column, stream, step) and the key (seed_lo,
+    seed_hi); its four words belong to keys 4 (k // 4) .. + 3, in order.
+    ld < 2^28 and 2 heads keep word 1 inside 32 bits.  The three element-wise
+    sites of a layer use `keep_mask` over the packed buffer [rows, ld], the
+    positional site `keep_mask` over the caller's [C, sum T]."""
+    seed, keys = int(seed) & (1 << 64) - 1, int(keys)
+    row = int(head) * int(ld) + int(query_column)
+    assert 0 <= row <= _MASK and keys >= 0
+    quads = np.arange((keys + 3) // 4, dtype=np.uint64)
+    words = philox4x32_10(
+        (quads, row, int(stream) & _MASK, int(step) & _MASK),
+        (seed & _MASK, seed >> 32))
+    words = np.stack(np.broadcast_arrays(*words), axis=1).ravel()
+    return words[:keys] >= np.uint32(threshold(p))
+
+
+def attention_segment_mask(seed, stream, step, p, ld, heads, offset, count):
+    """bool [heads, count, count] (head, query, key): `attention_keep_mask` of
+    every query of the segment whose first packed column is `offset`."""
+    seed, count = int(seed) & (1 << 64) - 1, int(count)
+    rows = (np.arange(int(heads), dtype=np.uint64)[:, None] * np.uint64(ld)
+            + np.uint64(offset) + np.arange(count, dtype=np.uint64)[None, :])
+    assert not rows.size or int(rows.max()) <= _MASK
+    quads = np.arange((count + 3) // 4, dtype=np.uint64)
+    words = philox4x32_10(
+        (quads[None, None, :], rows[:, :, None], int(stream) & _MASK,
+         int(step) & _MASK), (seed & _MASK, seed >> 32))
+    words = np.stack(np.broadcast_arrays(*words), axis=3).reshape(
+        int(heads), count, -1)
+    return words[:, :, :count] >= np.uint32(threshold(p))

@@ -10,12 +10,17 @@ Every utterance runs alone, as inference runs it: attention stays within an
 utterance, and the sinusoidal table (`weights.positional_encoding`) is
 gathered by the position inside the utterance.
 
-Deliberate deviation: dropout is the identity.  The reference's
-`TransformerEncoderLayer` trains with its internal dropout of 0.1 (attention
-weights, both residual branches, the feed-forward) and its
-`PositionalEncoding` with another 0.1; neither is drawn here (dropout inside
-the attention kernel is not built), so `train()` and `eval()` compute the
-same function.  `Config.dropout` (the conv stacks' switch) is refused.
+Dropout.  The reference's `TransformerEncoderLayer` trains with its internal
+dropout of 0.1 (attention weights, both residual branches, the feed-forward)
+and its `PositionalEncoding` with another 0.1: constants of the architecture.
+By default (`reference_dropout=False`) none of them is drawn and `train()`
+and `eval()` compute the same function - a deliberate deviation, kept as the
+default so that what exists keeps its bits.  With `reference_dropout=True` a
+model in training mode draws all five, as specified masks
+(`train/dropout.py`: `transformer_stream`, `keep_mask`,
+`attention_keep_mask`) of (`seed`, site, `self.steps`), through
+`ops.dropout` and `ops.encoder_layer_dropout`; in `eval()` it drops nothing.
+`Config.dropout` (the conv stacks' switch) is refused either way.
 """
 import collections
 import functools
@@ -27,6 +32,7 @@ from .. import config as cfg
 from .. import core as api
 from .. import ops  # noqa: F401  (registers torch.ops.emphases_amd)
 from .. import weights as weights_module
+from . import dropout as spec
 
 CHANNELS, HEADS = 80, 2     # the backward of encoder_layer
 
@@ -131,14 +137,22 @@ class _Layer(torch.nn.Module):
                 weight=state[f'{prefix}{name}.weight'],
                 bias=state[f'{prefix}{name}.bias']))
 
-    def forward(self, x, cu):
+    def forward(self, x, cu, dropout=None):
+        """`dropout` = (seed, stream_base, step): the layer in training mode
+        under the reference's dropout."""
         attention = self.self_attn
-        return torch.ops.emphases_amd.encoder_layer(
-            x, attention.in_proj_weight, attention.in_proj_bias,
+        tensors = (
+            attention.in_proj_weight, attention.in_proj_bias,
             attention.out_proj.weight, attention.out_proj.bias,
             self.norm1.weight, self.norm1.bias, self.linear1.weight,
             self.linear1.bias, self.linear2.weight, self.linear2.bias,
-            self.norm2.weight, self.norm2.bias, cu, HEADS)
+            self.norm2.weight, self.norm2.bias)
+        if dropout is None:
+            return torch.ops.emphases_amd.encoder_layer(x, *tensors, cu, HEADS)
+        seed, stream_base, step = dropout
+        return torch.ops.emphases_amd.encoder_layer_dropout(
+            x, *tensors, cu, HEADS, spec.TRANSFORMER_LAYER_DROPOUT, seed,
+            stream_base, step)
 
 
 @functools.lru_cache(maxsize=16)
@@ -161,6 +175,10 @@ class _Transformer(torch.nn.Module):
 
     def __init__(self, config, prefix, state):
         super().__init__()
+        self.streams = (
+            spec.transformer_stream(config, prefix),
+            [spec.transformer_stream(config, prefix, i, 'attention')
+             for i in range(config.layers)])
         self.model = torch.nn.Module()
         self.model.layers = torch.nn.ModuleList(
             _Layer(state, f'{prefix}.model.layers.{i}.')
@@ -170,33 +188,53 @@ class _Transformer(torch.nn.Module):
                 cfg.MAX_POSITIONS, config.channels)).t().contiguous(),
             persistent=False)
 
-    def forward(self, x, cu):
+    def forward(self, x, cu, dropout=None):
+        """`dropout` = (seed, step): training under the reference's dropout
+        (`PositionalEncoding`'s after the sum, then every layer's four)."""
         host = cu.detach().cpu().to(torch.int64).numpy()
         index = _positions(np.ascontiguousarray(host).tobytes(), str(x.device))
         x = x + self.encoding.index_select(1, index)
-        for layer in self.model.layers:
-            x = layer(x, cu)
+        if dropout is None:
+            for layer in self.model.layers:
+                x = layer(x, cu)
+            return x
+        seed, step = dropout
+        position, layers = self.streams
+        x = torch.ops.emphases_amd.dropout(
+            x, spec.TRANSFORMER_POSITION_DROPOUT, seed, position, step)
+        for layer, stream_base in zip(self.model.layers, layers):
+            x = layer(x, cu, (seed, stream_base, step))
         return x
 
 
 class TransformerModel(torch.nn.Module):
-    """`TransformerModel(config, checkpoint=None, seed=0)`; `forward(features
+    """`TransformerModel(config, checkpoint=None, seed=0,
+    reference_dropout=False)`; `forward(features
     [C_in, sum T], cu_frames, bounds [2, sum W], cu_words) -> logits [sum W]`,
     the utterances back to back (`cu_*`: N + 1 prefix sums, on the host), as
     `TorchModel`; `train.loss_fn` serves unchanged.
 
     downsample_location 'intermediate' or 'loss', every downsample_method;
-    80 channels, 2 heads, no dropout (module docstring).  The parameters carry
+    80 channels, 2 heads.  `reference_dropout=True` trains with the
+    reference's five dropouts (module docstring): the masks are a function
+    of `seed`, the site and `self.steps`, a plain int (0 at first; not a
+    parameter, not in `state_dict()`) that the caller sets or advances once
+    per optimizer update, so the same batch at the same `steps` gives the
+    same bits.  In `eval()`, and with the default False, nothing is dropped.
+    The parameters carry
     the reference's names and order (`weights.parameter_shapes`):
     `state_dict()` is read by `weights.load` and by every inference entry
     point's `checkpoint=`.  Without a checkpoint they are bitwise
     `initial_transformer_state(config, seed)`.  A segment longer than the
     5000-entry positional encoding raises ValueError."""
 
-    def __init__(self, config=None, checkpoint=None, seed=0):
+    def __init__(self, config=None, checkpoint=None, seed=0,
+                 reference_dropout=False):
         super().__init__()
         self.config = config = config or api.active_config()
         check_transformer_supported(config)
+        self.reference_dropout = bool(reference_dropout)
+        self.seed, self.steps = int(seed), 0
         if checkpoint is None:
             state = initial_transformer_state(config, seed)
         else:
@@ -214,11 +252,14 @@ class TransformerModel(torch.nn.Module):
         conv = torch.ops.emphases_amd.conv1d_same_act
         x = conv(features, self.input_layer.weight, self.input_layer.bias,
                  cu_frames, 'none')
-        x = self.frame_encoder(x, cu_frames)
+        dropout = None
+        if self.reference_dropout and self.training:
+            dropout = (self.seed, int(self.steps))
+        x = self.frame_encoder(x, cu_frames, dropout)
         x = torch.ops.emphases_amd.segment_reduce(
             x, bounds, cu_frames, cu_words, self.config.downsample_method)
         if self.config.has_decoder:
-            x = self.word_decoder(x, cu_words)
+            x = self.word_decoder(x, cu_words, dropout)
         x = conv(x, self.output_layer.weight, self.output_layer.bias,
                  cu_words, 'none')
         return x[0]

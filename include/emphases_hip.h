@@ -1568,6 +1568,51 @@ int emph_attention_backward(const float* qk, const float* v, const float* out,
                             int32_t heads, const int32_t* tiles, int32_t n_tiles,
                             int32_t tile_n, float* workspace, void* stream);
 
+/* The attention of TRAINING: emph_attention with key_counts == NULL and the
+ * dropout of nn.MultiheadAttention on the softmax weights
+ * (transformer.py:18-23 keeps torch's default dropout = 0.1):
+ *     O = (M o P scale) V,  P = softmax(Q K^T / sqrt(d))
+ * M is the specified mask of emphases_amd/train/dropout.py
+ * (`attention_keep_mask`), a pure function of its arguments: key quad k / 4
+ * of (head, packed query column) has the Philox-4x32-10 counter
+ * (k / 4, head ld + column, stream_id, step) under the key `seed`; the four
+ * words belong to keys 4 (k / 4) .. + 3 counted from the segment's first
+ * position; a weight is kept iff its word >= threshold(p) and kept weights are
+ * scaled by float32(1 / (1 - p)), as emph_dropout.  The mask is never stored.
+ *   qk, v, out  as emph_attention takes and leaves them
+ *   tiles       the 64-wide tile table of the walked axis (tile_n = 64)
+ * One launch, a kernel of its own on the layout of emph_attention_backward's
+ * query pass (fp32 MFMA, two loops over the keys: the row log-sum-exp, then
+ * the product); no atomics, the same inputs give the same bits.  Columns
+ * outside the segments are neither read nor written.  Any segment length
+ * >= 1; 0 <= p < 1 (p = 0 drops nothing; the bits need not be those of
+ * emph_attention, a different kernel).  Only channels 80 in 2 heads and
+ * ld < 2^28; anything else returns EMPH_ERANGE and launches nothing.
+ *
+ * emph_attention_dropout_backward: emph_attention_backward of that forward,
+ * with `out` the DROPPED output.  With P~ = M o P scale and
+ * D_i = sum_c dout[c][i] out[c][i] (= sum_j P_ij dP_ij still),
+ *     dV = P~^T dO     dS = P o (scale M o (dO V^T) - D)
+ * and dQ, dK from dS as before; both passes regenerate the mask from the
+ * counters (the key pass, whose lanes hold four queries of one key, draws one
+ * quad per lane and transposes the bits inside aligned groups of four lanes).
+ * `workspace` holds emph_attention_dropout_backward_workspace(ld, heads)
+ * floats, [3][heads][ld]: the row maximum (log2 units), D and 1 / sum - kept
+ * apart, as the forward keeps them, so that the weights of a row add up to 1
+ * whatever the size of the logits.  At p = 0 it IS emph_attention_backward,
+ * bit for bit. */
+int64_t emph_attention_dropout_backward_workspace(int64_t ld, int32_t heads);
+int emph_attention_dropout(const float* qk, const float* v, float* out, int64_t ld,
+                           int32_t channels, int32_t heads, const int32_t* tiles,
+                           int32_t n_tiles, int32_t tile_n, float p, uint64_t seed,
+                           uint32_t stream_id, uint32_t step, void* stream);
+int emph_attention_dropout_backward(const float* qk, const float* v, const float* out,
+                                    const float* dout, float* dqkv, int64_t ld,
+                                    int32_t channels, int32_t heads, const int32_t* tiles,
+                                    int32_t n_tiles, int32_t tile_n, float* workspace, float p,
+                                    uint64_t seed, uint32_t stream_id, uint32_t step,
+                                    void* stream);
+
 /* Backward of emph_add_layernorm (the post-LN residual under autograd).  `s`
  * [channels, ld] is the pre-norm sum x + r, whose statistics are recomputed
  * per column as the forward computes them (a constant column has

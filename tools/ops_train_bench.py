@@ -32,6 +32,16 @@ adds the launch timer's per-kernel times of `emph_attention` and
 heads of 40), the MFMA flops they execute over the 157.3 TFLOP/s fp32 peak,
 and torch's own `scaled_dot_product_attention` forward and backward on the
 same shapes with the backend torch picked.
+
+`--reference_dropout` (with `--architecture transformer`): three contenders
+in the same alternation - `ops_dropout`, the step of
+`TransformerModel(reference_dropout=True)` (the reference's five dropouts as
+specified masks, `steps` advanced per update), `ops`, the default model
+without dropout (the code path every earlier figure was taken on), and
+`torch_fp32_dropout`, `torch.nn.TransformerEncoder(dropout=0.1)` plus the
+positional dropout of 0.1 under autograd and Adam in float32.  `--kernels-out`
+then also times `emph_attention_dropout` and the two passes of
+`emph_attention_dropout_backward` (p = 0.1) beside the plain kernels.
 """
 import argparse
 import json
@@ -55,14 +65,17 @@ PEAK_FP32_MFMA = 157.3e12
 
 class TorchTransformer(torch.nn.Module):
     """`emphases.Model` under ARCHITECTURE 'transformer', 'intermediate' +
-    'sum', every dropout 0, on a batch of equal lengths (no padding mask)."""
+    'sum', on a batch of equal lengths (no padding mask); `dropout` is the
+    probability of the layers' dropouts and of the positional one (the
+    reference's 0.1), 0 for none."""
 
-    def __init__(self, config, state):
+    def __init__(self, config, state, dropout=0.):
         super().__init__()
         from emphases_amd import weights
+        self.dropout = dropout
         stack = lambda: torch.nn.TransformerEncoder(  # noqa: E731
             torch.nn.TransformerEncoderLayer(
-                80, 2, dim_feedforward=80, dropout=0.), config.layers,
+                80, 2, dim_feedforward=80, dropout=dropout), config.layers,
             enable_nested_tensor=False)
         self.input_layer = torch.nn.Conv1d(80, 80, 3, padding='same')
         self.frame_encoder = stack()
@@ -74,12 +87,16 @@ class TorchTransformer(torch.nn.Module):
             {name.replace('.model.', '.'): torch.from_numpy(value)
              for name, value in state.items()})
 
+    def positioned(self, x):
+        return torch.nn.functional.dropout(
+            x + self.encoding[:x.shape[0]], self.dropout, self.training)
+
     def forward(self, features, membership):
         x = self.input_layer(features).permute(2, 0, 1)            # [T, B, C]
-        x = self.frame_encoder(x + self.encoding[:x.shape[0]])
+        x = self.frame_encoder(self.positioned(x))
         words = torch.bmm(x.permute(1, 2, 0), membership)           # [B, C, W]
         words = words.permute(2, 0, 1)
-        words = self.word_decoder(words + self.encoding[:words.shape[0]])
+        words = self.word_decoder(self.positioned(words))
         return self.output_layer(words.permute(1, 2, 0))
 
 
@@ -98,8 +115,9 @@ def sdpa_backend(query, key, value):
         return f'unknown ({type(error).__name__})'
 
 
-def attention_kernels(path, items, frames):
-    """Per-kernel times of the attention forward and backward of one layer."""
+def attention_kernels(path, items, frames, dropout=False):
+    """Per-kernel times of the attention forward and backward of one layer
+    (`dropout`: of the masked kernels at p = 0.1 as well)."""
     from emphases_amd import ops, runtime
     device = torch.device('cuda', 0)
     layout = ops._layout(device, np.full(items, frames, dtype=np.int64))
@@ -113,8 +131,13 @@ def attention_kernels(path, items, frames):
     dqkv = torch.zeros(240, ld, device=device)
     lib = runtime.library()
     workspace = torch.empty(
-        int(lib.emph_attention_backward_workspace(ld, 2)), device=device)
+        int(lib.emph_attention_dropout_backward_workspace(ld, 2)),
+        device=device)
     times = {'emph_attention': [], 'backward_queries': [], 'backward_keys': []}
+    if dropout:
+        times.update({'emph_attention_dropout': [],
+                      'dropout_backward_queries': [],
+                      'dropout_backward_keys': []})
     for lap in range(8):
         with runtime.LaunchTimer() as timer:
             runtime.check(lib.emph_attention(
@@ -126,6 +149,17 @@ def attention_kernels(path, items, frames):
                 dqkv.data_ptr(), ld, 80, 2, tiles.data_ptr(), n_tiles, 64,
                 workspace.data_ptr(), runtime.stream()),
                 'emph_attention_backward')
+            if dropout:
+                runtime.check(lib.emph_attention_dropout(
+                    qk.data_ptr(), v.data_ptr(), out.data_ptr(), ld, 80, 2,
+                    tiles.data_ptr(), n_tiles, 64, 0.1, 0, 1, lap,
+                    runtime.stream()), 'emph_attention_dropout')
+                runtime.check(lib.emph_attention_dropout_backward(
+                    qk.data_ptr(), v.data_ptr(), out.data_ptr(),
+                    dout.data_ptr(), dqkv.data_ptr(), ld, 80, 2,
+                    tiles.data_ptr(), n_tiles, 64, workspace.data_ptr(), 0.1,
+                    0, 1, lap, runtime.stream()),
+                    'emph_attention_dropout_backward')
         if lap:                                     # (the first lap warms up)
             for name, value in zip(times, timer.microseconds):
                 times[name].append(float(value))
@@ -134,6 +168,11 @@ def attention_kernels(path, items, frames):
     flops = {'emph_attention': blocks * 22 * mfma,
              'backward_queries': blocks * (10 + 20 + 12) * mfma,
              'backward_keys': blocks * (20 + 24) * mfma}
+    # (the masked kernels execute the same products; the forward the query
+    # pass's two score loops and its 12 product tiles)
+    flops.update({'emph_attention_dropout': blocks * (10 + 10 + 12) * mfma,
+                  'dropout_backward_queries': flops['backward_queries'],
+                  'dropout_backward_keys': flops['backward_keys']})
     record = {'shape': {'utterances': items, 'positions': frames, 'heads': 2,
                         'head_dimension': 40},
               'device': torch.cuda.get_device_name(0), 'kernels': {}}
@@ -152,6 +191,11 @@ def attention_kernels(path, items, frames):
     total = record['kernels']['emph_attention_backward']
     total['fraction_of_fp32_mfma_peak'] = total['executed_mfma_flops'] / (
         total['us_median'] * 1e-6) / PEAK_FP32_MFMA
+    if dropout:
+        kernels = record['kernels']
+        kernels['emph_attention_dropout_backward'] = {
+            'us_median': kernels['dropout_backward_queries']['us_median'] +
+            kernels['dropout_backward_keys']['us_median']}
     # torch's own attention on the same shapes: [B, heads, T, d] float32
     query, key, value = (torch.randn(
         items, 2, frames, 40, device=device, generator=generator
@@ -220,6 +264,29 @@ def transformer_main(arguments):
         'torch_fp32': lambda: train_bench.torch_step(
             plain, plain_optimizer, None, device_features, membership,
             device_targets)}
+    if arguments.reference_dropout:
+        dropping = train.TransformerModel(
+            config, checkpoint=state, reference_dropout=True).cuda()
+        dropping.train()
+        dropping_optimizer = torch.optim.Adam(dropping.parameters())
+
+        def ops_dropout_step():
+            dropping_optimizer.zero_grad(set_to_none=True)
+            loss = train.loss_fn(dropping(*flat), flat_targets, 'bce')
+            loss.backward()
+            dropping_optimizer.step()
+            dropping.steps += 1
+            return loss.detach()
+
+        noisy = TorchTransformer(config, state, dropout=0.1).cuda()
+        noisy.train()
+        noisy_optimizer = torch.optim.Adam(noisy.parameters())
+        contenders = {
+            'ops_dropout': ops_dropout_step,
+            'ops': ops_step,
+            'torch_fp32_dropout': lambda: train_bench.torch_step(
+                noisy, noisy_optimizer, None, device_features, membership,
+                device_targets)}
     first = {}
     for name, function in contenders.items():
         first[name] = float(function().detach())
@@ -247,14 +314,20 @@ def transformer_main(arguments):
             for name, values in laps.items()},
         'ms_per_step_laps': laps}
     median = {name: record['ms_per_step'][name]['median'] for name in laps}
-    record['torch_fp32_over_ops'] = median['torch_fp32'] / median['ops']
+    if arguments.reference_dropout:
+        record['ops_dropout_over_ops'] = median['ops_dropout'] / median['ops']
+        record['torch_fp32_dropout_over_ops_dropout'] = \
+            median['torch_fp32_dropout'] / median['ops_dropout']
+    else:
+        record['torch_fp32_over_ops'] = median['torch_fp32'] / median['ops']
     print(json.dumps(record))
     if arguments.out:
         with open(arguments.out, 'w') as file:
             json.dump(record, file, indent=1)
             file.write('\n')
     if arguments.kernels_out:
-        attention_kernels(arguments.kernels_out, items, frames)
+        attention_kernels(arguments.kernels_out, items, frames,
+                          arguments.reference_dropout)
 
 
 def main():
@@ -262,6 +335,7 @@ def main():
     parser.add_argument('--architecture', default='convolution',
                         choices=('convolution', 'transformer'))
     parser.add_argument('--kernels-out', default=None)
+    parser.add_argument('--reference_dropout', action='store_true')
     parser.add_argument('--laps', type=int, default=7)
     parser.add_argument('--seconds', type=float, default=1.0)
     parser.add_argument('--steps', type=int, default=None)
