@@ -1,0 +1,181 @@
+"""The layouts the ops of one batch share: prefix sums to counts, the
+`batch.Plan` of featurised segments and of audio chunks, `_Layout` (a plan with
+its device metadata, tile tables and column indices) and the small LRUs that
+keep them per batch."""
+import collections
+import threading
+
+import numpy as np
+import torch
+
+from .. import batch
+from .. import config as cfg
+from .. import runtime
+
+GRAD_TILE = 64       # emph_conv_weight_grad_any, emph_segment_reduce_backward
+DIRECT_TILE = 64     # emph_conv1d of the device-packed path and of the data gradient
+PLAN_CACHE_SIZE = 16
+
+
+def _counts(cu):
+    """Per-segment counts (python ints) of a prefix-sum tensor."""
+    values = cu.detach().cpu().to(torch.int64).numpy()
+    if values.ndim != 1 or values.size < 1 or values[0] != 0 or \
+            np.any(np.diff(values) < 0):
+        raise ValueError('cu_* must be non-decreasing prefix sums that start at 0')
+    return np.diff(values).astype(np.int64), values
+
+
+def _device_index(tensor):
+    if not tensor.is_cuda:
+        raise runtime.LibraryError(
+            'emphases_amd ops run on an MI355X / HIP device only (no CPU '
+            'fallback): the tensor is on ' + str(tensor.device))
+    return tensor.device.index
+
+
+def _own_bounds(count, words, bounds):
+    """The `bounds` columns of each of `count` segments ([2, 0] without words)."""
+    if words is None:
+        return [np.zeros((2, 0), dtype=np.int64)] * count
+    cuts = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
+    return [bounds[:, first:last] for first, last in zip(cuts[:-1], cuts[1:])]
+
+
+def _frame_plan(frames, words=None, bounds=None):
+    """`batch.Plan` of already-featurised segments of `frames[i]` positions."""
+    segments = [
+        batch.Segment(index, 0, own.shape[1], 0, 0, int(count), own)
+        for index, (count, own) in enumerate(
+            zip(frames, _own_bounds(len(frames), words, bounds)))]
+    return batch.Plan(segments, [0] * len(segments), [0] * len(segments))
+
+
+def _chunk_plan(samples, edges, words=None, bounds=None,
+                source='mels.py:31-36'):
+    """`batch.Plan` of N audio chunks back to back (a chunk = an utterance
+    whose one segment starts behind the zero padding), `words[i]` words with
+    `bounds` in each; F_i = 1 + (S_i - 160) // 160 frames.  `source`: what the
+    refusal of a chunk too short for the reflect padding cites."""
+    if np.any(samples <= cfg.PADDING):
+        raise ValueError(f'a chunk needs more than 432 samples ({source})')
+    counts = [0] * len(samples) if words is None else words
+    segments = [
+        batch.Segment(
+            index, 0, int(count), cfg.PADDING, int(length),
+            1 + (int(length) + 2 * cfg.PADDING - cfg.NUM_FFT) // cfg.HOPSIZE,
+            own)
+        for index, (length, count, own) in enumerate(zip(
+            samples, counts, _own_bounds(len(samples), words, bounds)))]
+    return batch.Plan(segments, edges[:-1], samples)
+
+
+def _columns(offsets, counts, device):
+    """The library's packed columns of N back-to-back segments, as one index."""
+    if not len(counts):
+        return torch.zeros(0, dtype=torch.int64, device=device)
+    index = np.concatenate([np.arange(off, off + count, dtype=np.int64)
+                            for off, count in zip(offsets, counts)])
+    return torch.from_numpy(index).to(device)
+
+
+class _Layout:
+    """What the ops of one batch share: the `batch.Plan`, its integer metadata
+    on the device (name -> (view, size)), the frame tile tables (each uploaded
+    when an op first asks for its width, so a plan costs no more to build
+    than it did per call) and the device column indices of the scatter and
+    the gather."""
+
+    def __init__(self, plan, device):
+        self.plan = plan
+        host, offsets = plan.pack_metadata([])
+        self.buffer = torch.from_numpy(host).to(device)
+        self.meta = {name: (self.buffer[start:start + size], size)
+                     for name, (start, size) in offsets.items()}
+        self.meta['positions'] = (plan.total_frames, plan.total_words)
+        self.frame_columns = _columns(plan.frame_off, plan.frames, device)
+        self._word_columns = None
+        self.checked = {}
+
+    @property
+    def word_columns(self):
+        if self._word_columns is None:
+            self._word_columns = _columns(
+                self.plan.word_off, self.plan.words, self.buffer.device)
+        return self._word_columns
+
+    def view(self, name):
+        return self.meta[name][0]
+
+    def tiles(self, tile):
+        """(device tile table of the frame axis `tile` wide, its rows)."""
+        key = ('tiles', runtime.AXIS_FRAMES, tile)
+        if key not in self.meta:
+            host = np.ascontiguousarray(
+                self.plan.tiles(runtime.AXIS_FRAMES, tile)).ravel()
+            self.meta[key] = (
+                torch.from_numpy(host).to(self.buffer.device), host.size)
+        tiles, size = self.meta[key]
+        return tiles, size // runtime.TILE_FIELDS
+
+    @staticmethod
+    def scatter(x, columns, ld):
+        """Back-to-back columns -> the library's packed axis, zeros between
+        (one indexed copy, not one per segment: 64 segments cost 0.5 ms of
+        launches, tools/ops_cost.py).  The way back is
+        `packed.index_select(1, columns)`."""
+        packed = torch.zeros((x.shape[0], ld), dtype=torch.float32,
+                             device=x.device)
+        packed.index_copy_(
+            1, columns, x[:, :columns.numel()].to(torch.float32))
+        return packed
+
+
+class _Recent:
+    """A small LRU of what `make()` gives for a key (made outside the lock: a
+    refusal caches nothing, and two threads may both make one)."""
+
+    lock = threading.Lock()
+
+    def __init__(self, size):
+        self.size = size
+        self.entries = collections.OrderedDict()
+
+    def get(self, key, make):
+        with self.lock:
+            found = self.entries.get(key)
+            if found is not None:
+                self.entries.move_to_end(key)
+                return found
+        found = make()
+        with self.lock:
+            self.entries[key] = found
+            while len(self.entries) > self.size:
+                self.entries.popitem(last=False)
+        return found
+
+
+_layouts = _Recent(PLAN_CACHE_SIZE)
+_logmel_plans = _Recent(PLAN_CACHE_SIZE)
+
+
+def _layout(device, frames, words=None, bounds=None):
+    """The `_Layout` of segments of `frames[i]` positions (and `words[i]` words
+    with `bounds`), from a small LRU keyed by the VALUES of the arrays."""
+    key = (device.index, frames.tobytes(),
+           None if words is None else (words.tobytes(), bounds.tobytes()))
+    return _layouts.get(
+        key, lambda: _Layout(_frame_plan(frames, words, bounds), device))
+
+
+def _logmel_plan(cu_samples, device):
+    """(the chunk plan of `cu_samples`, its device frame columns), from a
+    small LRU keyed by the values of `cu_samples`: the forward and its
+    backward share one."""
+    samples, edges = _counts(cu_samples)
+
+    def make():
+        plan = _chunk_plan(
+            samples, edges, source='reflect padding, mels.py:31-36')
+        return plan, _columns(plan.frame_off, plan.frames, device)
+    return _logmel_plans.get((device.index, edges.tobytes()), make)

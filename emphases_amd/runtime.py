@@ -617,3 +617,12 @@ def conv_pack(weight):
         weight.ctypes.data, c_out, c_in, kernel_size, pack.ctypes.data),
         'emph_conv_pack')
     return pack
+
+
+def conv_pack_indices(indices):
+    """`conv_pack` of an index array [c_out, c_in, k] (int, < 2^24): the
+    pack is a pure permutation with zero padding, so packing the indices + 1
+    gives, minus 1, where every element of a pack comes from (-1: padding)."""
+    assert indices.max() + 1 < 1 << 24
+    packed = conv_pack((indices + 1).astype(np.float32))
+    return packed.astype(np.int64) - 1

@@ -330,15 +330,6 @@ def _tile_count(tiles):
     return tiles.numel() // runtime.TILE_FIELDS
 
 
-def _pack_indices(indices):
-    """`emph_conv_pack` of an index array [c_out, c_in, k] (int, < 2^24): the
-    pack is a pure permutation with zero padding, so packing the indices + 1
-    gives, minus 1, where every element of a pack comes from (-1: padding)."""
-    assert indices.max() + 1 < 1 << 24
-    packed = runtime.conv_pack((indices + 1).astype(np.float32))
-    return packed.astype(np.int64) - 1
-
-
 def gather_tables(config=cfg.DEFAULT):
     """The `emph_take` table of every pack of a step: int32 `index` into the
     flat parameter buffer (-1: zero), and {layer: (first, size)} of the forward
@@ -359,7 +350,7 @@ def gather_tables(config=cfg.DEFAULT):
             if direction == 'backward':
                 indices = np.ascontiguousarray(
                     indices.transpose(1, 0, 2)[:, :, ::-1])
-            piece = _pack_indices(indices)
+            piece = runtime.conv_pack_indices(indices)
             table[name] = (cursor, piece.size)
             pieces.append(piece)
             cursor += piece.size

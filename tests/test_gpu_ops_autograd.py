@@ -392,6 +392,37 @@ def test_device_packed_path_against_torch(c_in, c_out, k, activation):
         assert error <= allowed, (name, error, allowed)
 
 
+def test_host_pack_cache_answers_for_its_own_weight_alone():
+    """The host-pack path (untouched weights): a transposed view of a square
+    weight shares address, version and shape with it and must get a pack of
+    its own; an entry keeps no weight alive; and a new weight - very likely
+    at the dropped one's address - is convolved with its own values."""
+    import gc
+    import weakref
+    generator = torch.Generator().manual_seed(8080)
+    segments = [40, 23]
+    cu = torch.tensor([0, 40, 63])
+    x = torch.randn(80, sum(segments), generator=generator).to(device())
+    bias = torch.randn(80, generator=generator).to(device())
+
+    def conv(weight):
+        assert not ops._weight_changes(weight)
+        return torch.ops.emphases_amd.conv1d_same_act(
+            x, weight, bias, cu, 'relu')
+    w = (torch.randn(80, 80, 3, generator=generator) / 240 ** 0.5).to(device())
+    first = conv(w)
+    turned = conv(w.transpose(0, 1))
+    assert torch.equal(turned, conv(w.transpose(0, 1).contiguous()))
+    assert not torch.equal(turned, first)
+    alive = weakref.ref(w.untyped_storage())
+    del w
+    gc.collect()
+    assert alive() is None
+    values = torch.randn(80, 80, 3, generator=generator) / 240 ** 0.5
+    fresh, copy = values.to(device()), values.to(device())
+    assert torch.equal(conv(fresh), conv(copy))
+
+
 ###############################################################################
 # TorchModel
 ###############################################################################

@@ -404,6 +404,30 @@ def test_second_backward_raises_and_unasked_gradients_are_skipped():
     assert counts['norm2'] == 2 < counts['linear1'] < counts['all']
 
 
+def test_layer_engine_cache_answers_for_its_own_tensors_alone():
+    """The fused path (untouched parameters): `out_proj_weight.t()` shares
+    address, version and shape with `out_proj_weight` and must get an engine
+    of its own; an entry keeps no parameter alive."""
+    import gc
+    import weakref
+    leaves, _ = layer_leaves(requires_grad=False)
+    segments = [17, 64]
+    leaves[0] = leaves[0][:, :sum(segments)].contiguous()
+    cu = layer_cu(segments)
+
+    def layer(out_proj_weight):
+        return torch.ops.emphases_amd.encoder_layer(
+            *leaves[:3], out_proj_weight, *leaves[4:], cu, HEADS)
+    first = layer(leaves[3])
+    turned = layer(leaves[3].t())
+    assert torch.equal(turned, layer(leaves[3].t().contiguous()))
+    assert not torch.equal(turned, first)
+    alive = weakref.ref(leaves[3].untyped_storage())
+    del leaves
+    gc.collect()
+    assert alive() is None
+
+
 def test_backward_refuses_other_shapes():
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(5)

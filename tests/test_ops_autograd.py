@@ -174,6 +174,48 @@ def test_weight_caches_never_answer_for_another_tensor():
     assert cache.get(other, keys[1]) == 1 and cache.get(other, keys[2]) == 2
 
 
+def test_an_entry_of_several_tensors_answers_for_those_tensors_alone():
+    """The host packs of a convolution and the one-layer engine are made from
+    several tensors: a hit needs every one of their storages alive and the
+    asking tensors' own, and a strided view has a key of its own."""
+    import gc
+    cache = ops._ByStorage(4)
+    weight, bias = torch.zeros(4, 4, 3), torch.zeros(4)
+
+    def key(*pair):
+        return cache.key(pair, tuple(tensor._version for tensor in pair), 0)
+    entry = key(weight, bias)
+    assert cache.get((weight, bias), entry) is None
+    assert cache.put((weight, bias), entry, 'pack') == 'pack'
+    assert cache.get((weight, bias), entry) == 'pack'
+    assert cache.get((weight.detach(), bias), entry) == 'pack'
+    assert cache.get((weight, bias.detach()), entry) == 'pack'
+    assert cache.get([weight.detach(), bias.detach()], entry) == 'pack'
+    # either tensor replaced by another of the same shape: a miss, and the
+    # entry goes
+    for pair in ((torch.zeros(4, 4, 3), bias), (weight, torch.zeros(4))):
+        assert cache.get(pair, entry) is None
+        assert cache.get((weight, bias), entry) is None and not cache.entries
+        cache.put((weight, bias), entry, 'pack')
+    # either storage dead (a stand-in asks: the key is all that is left)
+    other_weight, other_bias = torch.zeros(4, 4, 3), torch.zeros(4)
+    del weight
+    gc.collect()
+    assert cache.get((other_weight, bias), entry) is None and not cache.entries
+    cache.put((other_weight, bias), entry, 'pack')
+    del bias
+    gc.collect()
+    assert cache.get((other_weight, other_bias), entry) is None
+    assert not cache.entries
+    # a transposed view shares address, version and shape with its base
+    square = torch.zeros(4, 4, 3)
+    turned = square.transpose(0, 1)
+    assert (turned.data_ptr(), turned._version, turned.shape) == \
+        (square.data_ptr(), square._version, square.shape)
+    assert cache.key(square) != cache.key(turned)
+    assert key(square, other_bias) != key(turned, other_bias)
+
+
 def test_weight_changes_follows_the_version_of_one_storage():
     import gc
     weight = torch.zeros(8, 4, 3)

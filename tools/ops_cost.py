@@ -2,7 +2,7 @@
 on the same batch (BASELINE configs[1]: 64 x 10 s): the ops convert between the caller's
 back-to-back layout and the library's packed one (one indexed copy each way); the plan of a
 batch, its device tables and the copies' column indices come from a small cache keyed by the
-`cu_*` / `bounds` values (`conv1d_same_act`, `segment_reduce`), the other ops build them per call.
+`cu_*` / `bounds` values (`prominence_forward` alone builds its plan per call).
 
     python tools/ops_cost.py          -> one JSON object on stdout
     python tools/ops_cost.py --parent <checkout of the parent commit, built> [--laps 5] [--out FILE]
@@ -175,11 +175,12 @@ def main():
     hidden = ops.conv1d_same_act(mel, weight, bias, frames, 'relu')
     result['op_segment_reduce_ms'] = clock(
         lambda: ops.segment_reduce(hidden, all_bounds, frames, words, 'sum'))
-    # the layout conversion alone: 64 slices in, 64 out
+    # the layout conversion alone: one indexed copy in, one out
     from emphases_amd import ops as module
-    result['scatter_plus_gather_ms'] = clock(lambda: module._gather(
-        module._scatter(mel, plan, plan.frame_off, plan.frames, plan.ld_frames),
-        plan.frame_off, plan.frames))
+    layout = module._layout(device, np.asarray(plan.frames, dtype=np.int64))
+    result['scatter_plus_gather_ms'] = clock(lambda: layout.scatter(
+        mel, layout.frame_columns, layout.plan.ld_frames).index_select(
+            1, layout.frame_columns))
     if arguments.parent:
         result['device'] = torch.cuda.get_device_name(0)
         result['alternating'] = alternate(arguments.parent, arguments.laps)
