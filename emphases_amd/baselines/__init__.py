@@ -73,13 +73,12 @@ def files_to_scores(method, text_files, audio_files, gpu=None,
 def _pitch_variance_files(opened, gpu, pitch_tracker):
     """Scores of a `FileBatch`, one call per sample rate."""
     times = opened.all_times()
-    loaded = [(audio if torch.is_tensor(audio) else audio.tensor(), rate)
-              for audio, rate in opened.all_audios()]
     scores = [None] * opened.count
-    for rate in sorted({rate for _, rate in loaded}):
-        chosen = [i for i, (_, r) in enumerate(loaded) if r == rate]
+    for rate, chosen, audios in opened.rate_groups():
         results = pitch_variance.from_alignments_and_audios(
-            [times[i] for i in chosen], [loaded[i][0] for i in chosen], rate,
+            [times[i] for i in chosen],
+            [audio if torch.is_tensor(audio) else audio.tensor()
+             for audio in audios], rate,
             None if gpu is None else gpu, pitch_tracker, on_device=False)
         for index, result in zip(chosen, results):
             scores[index] = result

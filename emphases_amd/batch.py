@@ -22,6 +22,7 @@ import numpy as np
 from . import alignment as alignment_module
 from . import config as cfg
 from . import convert
+from . import packed
 from . import runtime
 
 ALIGN = 16     # column alignment of every segment on the packed axes
@@ -287,11 +288,7 @@ class Plan:
         self.table = table
 
         # packed word-axis column of every word, in segment order
-        first = np.cumsum(words) - words
-        self._columns = (
-            np.repeat(self.word_off - first, words) +
-            np.arange(self.total_words, dtype=np.int64)) if count else \
-            np.zeros(0, dtype=np.int64)
+        self._columns = packed.column_index(self.word_off, words)
         self.bounds = np.zeros((2, self.ld_words), dtype=np.int32)
         self.word_segment = np.full(self.ld_words, -1, dtype=np.int32)
         if self.total_words:
@@ -535,6 +532,21 @@ class Plan:
                 'first': views['first'], 'lengths': views['lengths'],
                 'n_slots': slots}
         return packed, offsets
+
+
+def frame_plan(frames, words=None, bounds=None):
+    """`Plan` of already-featurised segments: segment i has `frames[i]`
+    positions and `words[i]` words, whose frame bounds lie back to back in
+    `bounds` (int64 [2, sum(words)]; no words at all when `words` is None).
+    Every segment is its own utterance and no audio belongs to it."""
+    frames = np.asarray(frames, dtype=np.int64).reshape(-1)
+    zeros = np.zeros(len(frames), dtype=np.int64)
+    if words is None:
+        words, bounds = zeros, np.zeros((2, 0), dtype=np.int64)
+    return Plan.from_columns(
+        np.arange(len(frames), dtype=np.int64), zeros, zeros, zeros, frames,
+        np.asarray(words, dtype=np.int64).reshape(-1),
+        np.asarray(bounds, dtype=np.int64).reshape(2, -1), zeros, zeros)
 
 
 class Pieces:

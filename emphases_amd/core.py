@@ -29,6 +29,7 @@ from . import batch
 from . import config as cfg
 from . import engine as engine_module
 from . import load
+from . import packed as packed_module
 from . import pipeline
 from . import runtime
 
@@ -46,6 +47,14 @@ def configure(config=None, **overrides):
 
 def active_config():
     return _ACTIVE[0]
+
+
+def _cache_key(checkpoint, gpu, config):
+    """(checkpoint path or None, device index, configuration): what the
+    engine and session caches are keyed by, whatever form the caller's
+    arguments came in."""
+    return (None if checkpoint is None else os.fspath(checkpoint),
+            runtime.device_index(gpu), config or active_config())
 
 
 @functools.lru_cache(maxsize=8)
@@ -68,12 +77,7 @@ def get_engine(checkpoint=None, gpu=None, config=None, conv_tile=None,
     direct form, which agrees with the Winograd kernels to 1e-6, not
     bitwise).  `precision`: 'f32', or one of the opt-in split-bf16 names of
     `engine.PRECISIONS`."""
-    device = runtime.require_gpu(gpu)
-    index = device.index if device.index is not None else \
-        torch.cuda.current_device()
-    checkpoint = None if checkpoint is None else os.fspath(checkpoint)
-    return _engine(checkpoint, index, config or active_config(), conv_tile,
-                   precision)
+    return _engine(*_cache_key(checkpoint, gpu, config), conv_tile, precision)
 
 
 ###############################################################################
@@ -127,12 +131,7 @@ def get_session(checkpoint=None, gpu=None, config=None, conv_tile=None,
                 precision='f32'):
     """Cached `session.Session` (batches in flight on their own streams) of
     the cached engine."""
-    device = runtime.require_gpu(gpu)
-    index = device.index if device.index is not None else \
-        torch.cuda.current_device()
-    checkpoint = None if checkpoint is None else os.fspath(checkpoint)
-    return _session(checkpoint, index, config or active_config(), conv_tile,
-                    precision)
+    return _session(*_cache_key(checkpoint, gpu, config), conv_tile, precision)
 
 
 def from_alignments_and_audios(alignments, audios, sample_rate=cfg.SAMPLE_RATE,
@@ -196,6 +195,14 @@ def from_text_and_audio(text, audio, sample_rate, checkpoint=None,
     raise NotImplementedError(
         'forced alignment (pyfoal/P2FA) is not part of the HIP hot path; '
         'align the transcript first and call from_alignment_and_audio')
+
+
+def _require_alignment_files(text_files):
+    """Transcripts (anything but .TextGrid / .json) would need the forced
+    aligner: what `from_text_and_audio` raises."""
+    for file in text_files:
+        if not str(file).endswith(('.TextGrid', '.json')):
+            from_text_and_audio(None, None, None)
 
 
 def from_file(text_file, audio_file, checkpoint=None, batch_size=None,
@@ -279,9 +286,7 @@ def files_to_scores(text_files, audio_files, session, batch_size=None,
     from . import files
     from . import session as session_module
     text_files, audio_files = list(text_files), list(audio_files)
-    for file in text_files:
-        if not str(file).endswith(('.TextGrid', '.json')):
-            from_text_and_audio(None, None, None)
+    _require_alignment_files(text_files)
     engine = session.engine
     ahead = session_module.FILE_BUFFERS - 2
     open_threads, write_threads = files.stage_threads(ahead)
@@ -326,14 +331,11 @@ def files_to_scores(text_files, audio_files, session, batch_size=None,
         _stamp('open.read', turn, begin)
         begin = time.perf_counter_ns()
         groups = []
-        rates = sorted({rate for _, rate in loaded})
         # (word-time tables, not alignment objects: nothing per file for the
         # interpreter's collector to trace; `deliver` builds what it asks for)
         alignments = opened.all_times()
-        for rate in rates:
-            chosen = [i for i, (_, r) in enumerate(loaded) if r == rate]
+        for rate, chosen, audios in opened.rate_groups(loaded):
             picked = [alignments[i] for i in chosen]
-            audios = [loaded[i][0] for i in chosen]
             plan = None
             if rate == cfg.SAMPLE_RATE and all(
                     a.dim() == 1 or a.shape[0] == 1 for a in audios):
@@ -406,9 +408,7 @@ def from_files_to_files(text_files, audio_files, output_prefixes=None,
     method = active_config().method
     if method != 'neural':
         from . import baselines
-        for file in text_files:
-            if not str(file).endswith(('.TextGrid', '.json')):
-                from_text_and_audio(None, None, None)
+        _require_alignment_files(text_files)
         baselines.files_to_scores(
             method, text_files, audio_files, gpu, utterances_per_batch,
             deliver_batch, pitch_tracker)
@@ -465,22 +465,13 @@ def postprocess(logits, config=None):
 
 def _packed_plan(frame_lengths, word_bounds, word_lengths):
     """Plan for already-featurised, padded `[B, C, T]` inputs."""
-    segments = []
-    for index, (frames, words) in enumerate(zip(frame_lengths, word_lengths)):
-        bounds = np.asarray(
-            word_bounds[index].cpu(), dtype=np.int64)[:, :int(words)]
-        segments.append(batch.Segment(
-            index, 0, int(words), 0, 0, int(frames), bounds))
-    return batch.Plan(
-        segments, [0] * len(segments), [0] * len(segments))
-
-
-def _pack(xs, plan, axis_offsets, counts, ld, device):
-    packed = torch.zeros(
-        (xs.shape[1], ld), dtype=torch.float32, device=device)
-    for index, (off, count) in enumerate(zip(axis_offsets, counts)):
-        packed[:, off:off + count] = xs[index, :, :count]
-    return packed
+    pairs = list(zip(frame_lengths, word_lengths))
+    bounds = [np.asarray(word_bounds[index].cpu(), dtype=np.int64)[
+        :, :int(words)] for index, (_, words) in enumerate(pairs)]
+    return batch.frame_plan(
+        [int(frames) for frames, _ in pairs],
+        [own.shape[1] for own in bounds],
+        np.concatenate(bounds + [np.zeros((2, 0), dtype=np.int64)], axis=1))
 
 
 def downsample(xs, word_bounds, word_lengths, config=None):
@@ -493,13 +484,9 @@ def downsample(xs, word_bounds, word_lengths, config=None):
     plan = _packed_plan([xs.shape[2]] * xs.shape[0], word_bounds, lengths)
     engine_module.check_bounds(plan, config.downsample_method)
     with torch.cuda.device(device):
-        host, offsets = plan.pack_metadata([])
-        meta = torch.from_numpy(host).to(device)
-        view = lambda name: meta[  # noqa: E731
-            offsets[name][0]:offsets[name][0] + offsets[name][1]]
-        packed = _pack(
-            xs.to(device, torch.float32), plan, plan.frame_off, plan.frames,
-            plan.ld_frames, device)
+        padded = packed_module.Padded(plan, device)
+        view = padded.view
+        packed = padded.pack(xs, 'frames')
         out = torch.zeros(
             (xs.shape[1], plan.ld_words), dtype=torch.float32, device=device)
         runtime.check(lib.emph_segment_reduce(
@@ -508,11 +495,7 @@ def downsample(xs, word_bounds, word_lengths, config=None):
             view('table').data_ptr(), view('word_segment').data_ptr(),
             plan.ld_words, runtime.REDUCTIONS[config.downsample_method],
             runtime.stream()), 'emph_segment_reduce')
-    result = torch.zeros(
-        (xs.shape[0], xs.shape[1], max(lengths) if lengths else 0),
-        dtype=torch.float32, device=device)
-    for index, (off, count) in enumerate(zip(plan.word_off, plan.words)):
-        result[index, :, :count] = out[:, off:off + count]
+        result = padded.unpack(out, 'words', max(lengths) if lengths else 0)
     return result if xs.is_cuda else result.cpu()
 
 
@@ -564,14 +547,10 @@ def upsample(xs, word_bounds, word_lengths, frame_lengths, config=None):
     plan = _packed_plan(frames, torch.from_numpy(bounds), lengths)
     tile_request = (runtime.AXIS_FRAMES, 64)
     with torch.cuda.device(device):
-        host, offsets = plan.pack_metadata([tile_request])
-        meta = torch.from_numpy(host).to(device)
-        view = lambda name: meta[  # noqa: E731
-            offsets[name][0]:offsets[name][0] + offsets[name][1]]
+        padded = packed_module.Padded(plan, device, [tile_request])
+        view = padded.view
         tiles = view(('tiles',) + tile_request)
-        packed = _pack(
-            xs.to(device, torch.float32), plan, plan.word_off, plan.words,
-            plan.ld_words, device)
+        packed = padded.pack(xs, 'words')
         out = torch.zeros(
             (xs.shape[1], plan.ld_frames), dtype=torch.float32, device=device)
         runtime.check(lib.emph_upsample(
@@ -581,11 +560,7 @@ def upsample(xs, word_bounds, word_lengths, frame_lengths, config=None):
             tiles.numel() // runtime.TILE_FIELDS,
             runtime.UPSAMPLE_METHODS[config.upsample_method],
             runtime.stream()), 'emph_upsample')
-        result = torch.zeros(
-            (xs.shape[0], xs.shape[1], max(frames) if frames else 0),
-            dtype=torch.float32, device=device)
-        for index, (off, count) in enumerate(zip(plan.frame_off, plan.frames)):
-            result[index, :, :count] = out[:, off:off + count]
+        result = padded.unpack(out, 'frames', max(frames) if frames else 0)
     return result if xs.is_cuda else result.cpu()
 
 
@@ -663,17 +638,12 @@ class Model:
         plan = _packed_plan(
             [int(n) for n in frame_lengths], word_bounds,
             [int(n) for n in word_lengths])
-        with torch.cuda.device(device), engine.lock:
-            packed = _pack(
-                features.to(device, torch.float32), plan, plan.frame_off,
-                plan.frames, plan.ld_frames, device)
-            _, logits = engine.forward(None, plan, features=packed)
-            logits = logits.clone()
         width = int(max(int(n) for n in word_lengths))
-        result = torch.zeros(
-            (features.shape[0], 1, width), dtype=torch.float32, device=device)
-        for index, (off, count) in enumerate(zip(plan.word_off, plan.words)):
-            result[index, 0, :count] = logits[off:off + count]
+        with torch.cuda.device(device), engine.lock:
+            padded = packed_module.Padded(plan, device)
+            _, logits = engine.forward(
+                None, plan, features=padded.pack(features, 'frames'))
+            result = padded.unpack(logits[None], 'words', width)
         return result if features.is_cuda else result.cpu()
 
 

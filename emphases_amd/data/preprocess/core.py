@@ -232,16 +232,14 @@ def survey(opened):
 
 
 def _room(lane, name, numel, dtype, pinned=False):
-    """A buffer of the lane that only grows (the batches of a run differ in
-    size: an exact fit would be a new allocation per batch)."""
+    """A buffer of the lane that only grows (`session.grown`), kept in the
+    lane engine's workspace."""
+    from ... import session
     store = lane.engine._workspace
-    tensor = store.get(('preprocess', name))
-    if tensor is None or tensor.numel() < numel:
-        size = max(int(numel), 1) * 5 // 4
-        tensor = torch.empty(size, dtype=dtype).pin_memory() if pinned else \
-            torch.empty(size, dtype=dtype, device=lane.device)
-        store[('preprocess', name)] = tensor
-    return tensor
+    store[('preprocess', name)] = session.grown(
+        store.get(('preprocess', name)), numel, dtype,
+        None if pinned else lane.device)
+    return store[('preprocess', name)]
 
 
 def _per_file(audio_file, mel_file, loudness_file):
@@ -300,6 +298,7 @@ def from_files_to_files(audio_files, mel_files=None, loudness_files=None,
     (`whole_audio_plan`), with nothing written."""
     from ... import engine as engine_module
     from ... import files
+    from ... import load
     from ... import session as session_module
     audio_files = [os.fspath(file) for file in audio_files]
     count = len(audio_files)
@@ -328,10 +327,9 @@ def from_files_to_files(audio_files, mel_files=None, loudness_files=None,
     lengths, formats = survey(opened)
     _stamp('headers', 0, start)
 
-    device = runtime.require_gpu(gpu)
-    index = device.index if device.index is not None else \
-        torch.cuda.current_device()
+    index = runtime.device_index(gpu)
     session = _session(index)
+    device = session.engine.device
     mel_config, loud_config = _feature_configs(core.active_config())
     # rows of the packed matrix: the mel rows, then the loudness row
     groups, configs, row = [], [], 0
@@ -356,12 +354,10 @@ def from_files_to_files(audio_files, mel_files=None, loudness_files=None,
     def open_batch(position):
         begin = time.perf_counter_ns()
         dtype, chosen = batches[position]
-        item = 2 if dtype == torch.int16 else 4
+        item = load.itemsize(dtype)
         samples = lengths[chosen]
         nbytes = samples * item
-        padded = (nbytes + 3) // 4 * 4
-        where = np.cumsum(padded) - padded
-        total = int(padded.sum())
+        where, total = files.aligned_placement(nbytes)
         with torch.cuda.device(device):
             staging = session.file_buffer(position, total)
         opened.read(chosen.astype(np.int32), where, nbytes,

@@ -115,6 +115,22 @@ def pool_near(cpus):
         array.ctypes.data, len(array)), 'emph_files_affinity')
 
 
+def aligned_placement(nbytes):
+    """Where entries of `nbytes[k]` bytes lie back to back with every start
+    4-byte aligned (a float32 view of any of them is legal, and odd counts of
+    16-bit samples leave a gap of two bytes): (byte offsets int64 [n], bytes in
+    all)."""
+    padded = (np.asarray(nbytes, dtype=np.int64) + 3) // 4 * 4
+    return np.cumsum(padded) - padded, int(padded.sum())
+
+
+def native_header(code, channels, bits):
+    """Whether a WAVE header (scalars, or arrays of them) is of the kind the
+    library reads itself: mono 16-bit PCM or mono float32."""
+    return (channels == 1) & (
+        ((code == 1) & (bits == 16)) | ((code == 3) & (bits == 32)))
+
+
 class FileAudio:
     """Stands in for the 1-D tensor of a mono 16-bit PCM / float32 WAVE file
     whose samples have not been read: the session reads them straight into its
@@ -283,7 +299,7 @@ class FileBatch:
             return self._audios[index], self._audios[index].rate
         _, _, _, _, _, code, channels, rate, bits, _, nbytes, _ = \
             self.sizes[index].tolist()
-        if channels == 1 and (code, bits) in ((1, 16), (3, 32)):
+        if native_header(code, channels, bits):
             dtype = torch.int16 if code == 1 else torch.float32
             self._audios[index] = FileAudio(
                 self, index, nbytes // (bits // 8), dtype, rate)
@@ -319,8 +335,7 @@ class FileBatch:
         for index, row in enumerate(rows):
             status, code, channels, rate, bits, nbytes = \
                 row[0], row[5], row[6], row[7], row[8], row[10]
-            if status & 2 or channels != 1 or \
-                    (code, bits) not in ((1, 16), (3, 32)):
+            if status & 2 or not native_header(code, channels, bits):
                 result.append(self.audio(index))
                 continue
             if self._audios[index] is None:
@@ -330,33 +345,40 @@ class FileBatch:
             result.append((self._audios[index], rate))
         return result
 
+    def rate_groups(self, loaded=None):
+        """(sample rate, indices of the files at that rate, their audios) by
+        rising rate - one submission each, since a batch is resampled as a
+        whole.  `loaded`: `all_audios()` when the caller has it already."""
+        loaded = self.all_audios() if loaded is None else loaded
+        for rate in sorted({rate for _, rate in loaded}):
+            chosen = [i for i, (_, r) in enumerate(loaded) if r == rate]
+            yield rate, chosen, [loaded[i][0] for i in chosen]
+
     def read_all(self, staging):
         """Read the samples of every `FileAudio` of the batch back to back
         into `staging` (a pinned uint8 tensor, on whatever thread): the
         session then sends them to the device straight from there
         (`Session` needs no copy of its own).  Returns the bytes used."""
         members = [audio for audio in self._audios if audio is not None]
-        nbytes = [audio.shape[0] * (2 if audio.dtype == torch.int16 else 4)
+        nbytes = [audio.shape[0] * load.itemsize(audio.dtype)
                   for audio in members]
-        where = np.concatenate([[0], np.cumsum(
-            [(n + 3) // 4 * 4 for n in nbytes])]).astype(np.int64)
-        if int(where[-1]) > staging.numel():
+        where, total = aligned_placement(nbytes)
+        if total > staging.numel():
             raise ValueError('staging buffer too small')
         if members:
-            self.read([audio.index for audio in members], where[:-1], nbytes,
+            self.read([audio.index for audio in members], where, nbytes,
                       staging.data_ptr())
-        for audio, offset in zip(members, where[:-1]):
-            audio.staged = int(offset)
+        for audio, offset in zip(members, where.tolist()):
+            audio.staged = offset
         self.staging = staging
-        return int(where[-1])
+        return total
 
     def native_audio(self):
         """bool [count]: files whose samples the library reads itself (mono
         16-bit PCM or float32; `all_audios` gives a `FileAudio` for them)."""
         sizes = self.sizes
-        return ((sizes[:, 0] & 2) == 0) & (sizes[:, 6] == 1) & (
-            ((sizes[:, 5] == 1) & (sizes[:, 8] == 16)) |
-            ((sizes[:, 5] == 3) & (sizes[:, 8] == 32)))
+        return ((sizes[:, 0] & 2) == 0) & native_header(
+            sizes[:, 5], sizes[:, 6], sizes[:, 8])
 
     def staged_format(self, sample_rate):
         """torch.int16 / torch.float32 when EVERY file of the batch is one the
@@ -380,9 +402,8 @@ class FileBatch:
         sizes = self.sizes
         nbytes = np.ascontiguousarray(sizes[:, 10])
         lengths = nbytes // (sizes[:, 8] // 8)
-        padded = (nbytes + 3) // 4 * 4
-        where = np.cumsum(padded) - padded
-        if int(where[-1] + padded[-1]) > staging.numel():
+        where, total = aligned_placement(nbytes)
+        if total > staging.numel():
             raise ValueError('staging buffer too small')
         self.read(np.arange(self.count, dtype=np.int32), where, nbytes,
                   staging.data_ptr())
@@ -392,7 +413,7 @@ class FileBatch:
     def audio_bytes(self):
         """Bytes `read_all` needs (every file's samples, 4-byte aligned)."""
         native = self.native_audio()
-        return int(((self.sizes[native, 10] + 3) // 4 * 4).sum())
+        return aligned_placement(self.sizes[native, 10])[1]
 
     def read(self, indices, where, nbytes, destination):
         """Samples of files `indices` to host address `destination +

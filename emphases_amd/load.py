@@ -23,6 +23,12 @@ from . import config as cfg
 FORMATS = {(1, 8), (1, 16), (1, 24), (1, 32), (3, 32), (3, 64)}
 
 
+def itemsize(dtype):
+    """Bytes per sample of the two formats that travel to the device as they
+    are: 16-bit PCM (torch.int16) and float32."""
+    return 2 if dtype == torch.int16 else 4
+
+
 def _walk(handle, file):
     """ONE chunk walker for `wav` and `wav_info` (seeks, no sample is read):
     `(code, channels, rate, bits, data offset, data bytes)`.  The LAST `fmt `

@@ -10,6 +10,7 @@ import torch
 
 from .. import batch
 from .. import config as cfg
+from .. import packed
 from .. import runtime
 
 GRAD_TILE = 64       # emph_conv_weight_grad_any, emph_segment_reduce_backward
@@ -42,13 +43,7 @@ def _own_bounds(count, words, bounds):
     return [bounds[:, first:last] for first, last in zip(cuts[:-1], cuts[1:])]
 
 
-def _frame_plan(frames, words=None, bounds=None):
-    """`batch.Plan` of already-featurised segments of `frames[i]` positions."""
-    segments = [
-        batch.Segment(index, 0, own.shape[1], 0, 0, int(count), own)
-        for index, (count, own) in enumerate(
-            zip(frames, _own_bounds(len(frames), words, bounds)))]
-    return batch.Plan(segments, [0] * len(segments), [0] * len(segments))
+_frame_plan = batch.frame_plan
 
 
 def _chunk_plan(samples, edges, words=None, bounds=None,
@@ -70,13 +65,7 @@ def _chunk_plan(samples, edges, words=None, bounds=None,
     return batch.Plan(segments, edges[:-1], samples)
 
 
-def _columns(offsets, counts, device):
-    """The library's packed columns of N back-to-back segments, as one index."""
-    if not len(counts):
-        return torch.zeros(0, dtype=torch.int64, device=device)
-    index = np.concatenate([np.arange(off, off + count, dtype=np.int64)
-                            for off, count in zip(offsets, counts)])
-    return torch.from_numpy(index).to(device)
+_columns = packed.columns
 
 
 class _Layout:
@@ -118,17 +107,7 @@ class _Layout:
         tiles, size = self.meta[key]
         return tiles, size // runtime.TILE_FIELDS
 
-    @staticmethod
-    def scatter(x, columns, ld):
-        """Back-to-back columns -> the library's packed axis, zeros between
-        (one indexed copy, not one per segment: 64 segments cost 0.5 ms of
-        launches, tools/ops_cost.py).  The way back is
-        `packed.index_select(1, columns)`."""
-        packed = torch.zeros((x.shape[0], ld), dtype=torch.float32,
-                             device=x.device)
-        packed.index_copy_(
-            1, columns, x[:, :columns.numel()].to(torch.float32))
-        return packed
+    scatter = staticmethod(packed.scatter)
 
 
 class _Recent:

@@ -345,6 +345,13 @@ def require_gpu(device=None):
     return torch.device(device)
 
 
+def device_index(device=None):
+    """Index of the HIP device `require_gpu(device)` resolves to."""
+    device = require_gpu(device)
+    return device.index if device.index is not None else \
+        torch.cuda.current_device()
+
+
 def check(status, name):
     if status != 0:
         message = library().emph_last_error().decode('utf-8', 'replace')

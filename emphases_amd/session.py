@@ -20,6 +20,7 @@ are staged and transferred as they are - half the bytes - and converted by the
 front-end kernel (identical scores: x / 32768 is exact).
 """
 import collections
+import contextlib
 import os
 import threading
 
@@ -79,6 +80,66 @@ def mono(audio):
     return audio
 
 
+def grown(buffer, numel, dtype=torch.uint8, device=None):
+    """`buffer` when it holds `numel` elements, else a new one with a quarter
+    to spare - THE buffer that only grows (batches differ in size: an exact
+    fit would be a new allocation, or milliseconds of pinning, per batch).
+    `device` None: pinned host memory."""
+    if buffer is not None and buffer.numel() >= numel:
+        return buffer
+    size = max(int(numel), 1) * 5 // 4
+    if device is None:
+        return torch.empty(size, dtype=dtype).pin_memory()
+    return torch.empty(size, dtype=dtype, device=device)
+
+
+def runs(where, nbytes):
+    """(first, last + 1) index arrays of the maximal runs of entries that lie
+    back to back: entry k + 1 starts at byte `where[k] + nbytes[k]`.  `where`
+    [n], or [n, spaces] when the entries are placed in several address spaces
+    at once (a source and a destination): a run is one in all of them."""
+    nbytes = np.asarray(nbytes, dtype=np.int64)
+    count = len(nbytes)
+    if not count:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    where = np.asarray(where, dtype=np.int64).reshape(count, -1)
+    cuts = np.nonzero(np.any(
+        where[1:] != where[:-1] + nbytes[:-1, None], axis=1))[0] + 1
+    return np.concatenate([[0], cuts]), np.concatenate([cuts, [count]])
+
+
+def send_runs(target, target_where, source, source_where, nbytes):
+    """Entries of `nbytes[k]` bytes from byte `source_where[k]` of the pinned
+    uint8 tensor `source` to byte `target_where[k]` of the device uint8 tensor
+    `target`, on the current stream: one DMA per run of entries that lie back
+    to back on both sides.  Nothing here is per entry."""
+    nbytes = np.asarray(nbytes, dtype=np.int64)
+    where = np.stack([np.asarray(source_where, dtype=np.int64),
+                      np.asarray(target_where, dtype=np.int64)], axis=1)
+    first, last = runs(where, nbytes)
+    sizes = where[last - 1, 0] + nbytes[last - 1] - where[first, 0]
+    for (start, to), size in zip(where[first].tolist(), sizes.tolist()):
+        target[to:to + size].copy_(
+            source[start:start + size], non_blocking=True)
+
+
+def host_gather(sources, nbytes, where, base, threads):
+    """`sources[k]` (contiguous host tensors) to host address `base +
+    where[k]`, `nbytes[k]` bytes each, on the library's persistent pool of
+    copy threads (`emph_host_gather`; numpy copies from a Python thread pool
+    reach 58 GB/s and torch's CPU copy_ into a slice of a large tensor a tenth
+    of that, tools/h2d_paths.py)."""
+    from . import runtime
+    # (named: an array that is only a temporary of the argument list is freed
+    # before the call reads it)
+    pointers = np.array([a.data_ptr() for a in sources], dtype=np.int64)
+    nbytes = np.ascontiguousarray(nbytes, dtype=np.int64)
+    where = np.ascontiguousarray(where, dtype=np.int64)
+    runtime.check(runtime.library().emph_host_gather(
+        pointers.ctypes.data, nbytes.ctypes.data, where.ctypes.data,
+        len(sources), base, int(threads)), 'emph_host_gather')
+
+
 class _Lane:
     """One batch in flight."""
 
@@ -100,147 +161,96 @@ class _Lane:
         self.layouts = collections.OrderedDict()
 
     def _reserve(self, nbytes, words):
-        if self.staging is None or self.staging.numel() < nbytes:
-            size = max(nbytes, 1) * 5 // 4
-            self.staging = torch.empty(size, dtype=torch.uint8).pin_memory()
+        staging = grown(self.staging, nbytes)
+        if staging is not self.staging:
+            self.staging = staging
             self.audio = torch.empty(
-                size, dtype=torch.uint8, device=self.device)
+                staging.numel(), dtype=torch.uint8, device=self.device)
             self.layouts.clear()      # captured graphs point at the old buffer
-        if self.result is None or self.result.numel() < words:
-            self.result = torch.empty(
-                max(words, 1) * 5 // 4, dtype=torch.float32).pin_memory()
+        self.result = grown(self.result, words, torch.float32)
 
     def stage(self, audios, lengths, dtype, raw=False):
         """Packed device tensor of all utterances (dtype float32 or int16),
         enqueued on this lane's stream.  `raw`: into the buffer that holds
-        audio at the caller's rate, in front of the resampler."""
-        item = 2 if dtype == torch.int16 else 4
-        total = int(sum(lengths))
-        offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        audio at the caller's rate, in front of the resampler.
+
+        A batch whose host utterances all lie in pinned memory already
+        (`FileBatch.read_all`) is sent from where it lies.  Otherwise what is
+        on the host is first put into the lane's pinned staging buffer, in
+        the place it has in the packed tensor - host tensors and staged files
+        by `host_gather`, files still on disk by the library's readers
+        (`FileBatch.read`) - a few pieces at a time, each sent as soon as it
+        is filled, so the DMA of one runs under the filling of the next.
+        Device-resident utterances are copied last."""
+        item = load.itemsize(dtype)
+        nbytes = np.asarray(lengths, dtype=np.int64) * item
+        where = np.cumsum(nbytes) - nbytes
+        total = int(nbytes.sum())
         if raw:
-            if self.raw is None or self.raw.numel() < total * item:
-                self.raw = torch.empty(
-                    max(total * item, 1) * 5 // 4, dtype=torch.uint8,
-                    device=self.device)
-            buffer = self.raw
-        else:
-            buffer = self.audio
-        device_view = buffer[:max(total, 1) * item].view(dtype)[:total]
-        on_host = [i for i, a in enumerate(audios) if not a.is_cuda]
-        host_view = self.staging[:max(total, 1) * item].view(dtype)[:total]
-        if any(not torch.is_tensor(audios[i]) for i in on_host):
-            return self._stage_files(
-                audios, lengths, item, offsets, host_view, device_view)
-        # The gather runs in the library (`emph_host_gather`: a persistent pool
-        # of copy threads; numpy copies from a Python thread pool reach 58 GB/s
-        # and torch's CPU copy_ into a slice of a large tensor a tenth of that,
-        # tools/h2d_paths.py).  A few pieces, each sent to the device as soon as
-        # it is gathered, so the DMA of one runs under the gather of the next.
-        from . import runtime
-        lib = runtime.library()
-        sources = [host_contiguous(audios[i]) for i in on_host]
-        pointers = np.array([a.data_ptr() for a in sources], dtype=np.int64)
-        nbytes = np.array([lengths[i] * item for i in on_host], dtype=np.int64)
-        where = np.array([offsets[i] * item for i in on_host], dtype=np.int64)
-        threads = max(1, min(COPY_THREADS, total * item // (3 << 20)))
-        pieces = max(1, min(4, len(on_host), total * item // (8 << 20)))
-        edges = np.linspace(0, len(on_host), pieces + 1).astype(int)
-        base = host_view.data_ptr()
-        for lo, hi in zip(edges[:-1], edges[1:]):
-            if hi == lo:
-                continue
-            runtime.check(lib.emph_host_gather(
-                pointers[lo:hi].ctypes.data, nbytes[lo:hi].ctypes.data,
-                where[lo:hi].ctypes.data, int(hi - lo), base, int(threads)),
-                'emph_host_gather')
-            # contiguous runs of the piece go to the device
-            first = lo
-            for k in range(lo + 1, hi + 1):
-                if k == hi or on_host[k] != on_host[k - 1] + 1:
-                    start = int(offsets[on_host[first]])
-                    stop = int(offsets[on_host[k - 1] + 1])
-                    device_view[start:stop].copy_(
-                        host_view[start:stop], non_blocking=True)
-                    first = k
+            self.raw = grown(self.raw, total, device=self.device)
+        buffer = self.raw if raw else self.audio
+        target = buffer[:total]
+        staged, fill, resident = [], [], []
         for i, audio in enumerate(audios):
             if audio.is_cuda:
-                device_view[offsets[i]:offsets[i + 1]].copy_(
-                    audio, non_blocking=True)
-        return device_view
-
-
-    def _stage_files(self, audios, lengths, item, offsets, host_view,
-                     device_view):
-        """`stage` for a batch whose audio is still on disk
-        (`files.FileAudio`): the library's threads read the data chunks
-        straight into the pinned staging buffer (`emph_files_read_audio`), a
-        few pieces at a time, each sent to the device as soon as it is read;
-        tensors among them take the copy path."""
-        from . import runtime
-        count = len(audios)
-        if all(not torch.is_tensor(audio) and audio.staged is not None
-               for audio in audios):
-            # already read into the batch's own pinned buffer (by the opener
-            # thread of core.files_to_scores): one DMA per run of files that
-            # sit back to back there
-            dtype = device_view.dtype
-            first = 0
-            for k in range(1, count + 1):
-                previous = audios[k - 1]
-                if k < count and audios[k].batch is previous.batch and \
-                        audios[k].staged == previous.staged + \
-                        lengths[k - 1] * item:
-                    continue
-                head = audios[first]
-                start, stop = int(offsets[first]), int(offsets[k])
-                source = head.batch.staging[
-                    head.staged:head.staged + (stop - start) * item]
-                device_view[start:stop].copy_(
-                    source.view(dtype), non_blocking=True)
-                first = k
-            return device_view
-        base = host_view.data_ptr()
-        pieces = max(1, min(4, count, int(offsets[-1]) * item // (8 << 20)))
-        edges = np.linspace(0, count, pieces + 1).astype(int)
+                resident.append(i)
+            elif getattr(audio, 'staged', None) is not None:
+                staged.append(i)
+            else:
+                fill.append(i)
+        if fill and staged:
+            # a mixed batch: the staged files join the gather (a copy between
+            # pinned buffers, no second read), so a piece still leaves in one
+            # DMA where staged files and host tensors alternate
+            fill, staged = sorted(fill + staged), []
+        by_buffer = {}
+        for i in staged:
+            by_buffer.setdefault(id(audios[i].batch), []).append(i)
+        for members in by_buffer.values():
+            send_runs(target, where[members],
+                      audios[members[0]].batch.staging,
+                      [audios[i].staged for i in members], nbytes[members])
+        threads = max(1, min(COPY_THREADS, total // (3 << 20)))
+        pieces = max(1, min(4, len(fill), total // (8 << 20)))
+        edges = np.linspace(0, len(fill), pieces + 1).astype(int)
         for lo, hi in zip(edges[:-1], edges[1:]):
             if hi == lo:
                 continue
-            by_batch = {}
-            tensors = []
-            for i in range(lo, hi):
-                audio = audios[i]
-                if torch.is_tensor(audio):
-                    if not audio.is_cuda:
-                        tensors.append(i)
-                    continue
-                by_batch.setdefault(id(audio.batch), (audio.batch, []))[1] \
-                    .append(i)
-            for batch_files, members in by_batch.values():
-                batch_files.read(
-                    [audios[i].index for i in members],
-                    [int(offsets[i]) * item for i in members],
-                    [lengths[i] * item for i in members], base)
-            if tensors:
-                sources = [host_contiguous(audios[i]) for i in tensors]
-                # (named: an array that is only a temporary of the argument
-                # list is freed before the call reads it)
-                pointers = np.array(
-                    [a.data_ptr() for a in sources], dtype=np.int64)
-                sizes = np.array(
-                    [lengths[i] * item for i in tensors], dtype=np.int64)
-                where = np.array(
-                    [int(offsets[i]) * item for i in tensors], dtype=np.int64)
-                runtime.check(runtime.library().emph_host_gather(
-                    pointers.ctypes.data, sizes.ctypes.data, where.ctypes.data,
-                    len(tensors), base, COPY_THREADS), 'emph_host_gather')
-            start, stop = int(offsets[lo]), int(offsets[hi])
-            device_view[start:stop].copy_(
-                host_view[start:stop], non_blocking=True)
-        for i, audio in enumerate(audios):
-            if torch.is_tensor(audio) and audio.is_cuda:
-                device_view[offsets[i]:offsets[i + 1]].copy_(
-                    audio, non_blocking=True)
-        return device_view
+            members = fill[lo:hi]
+            self._fill(audios, members, where, nbytes, threads)
+            send_runs(target, where[members], self.staging, where[members],
+                      nbytes[members])
+        packed = buffer[:max(total, item)].view(dtype)[:total // item]
+        for i in resident:
+            first = int(where[i]) // item
+            packed[first:first + lengths[i]].copy_(
+                audios[i], non_blocking=True)
+        return packed
+
+    def _fill(self, audios, members, where, nbytes, threads):
+        """Utterances `members` (host tensors, files staged elsewhere, files
+        not yet read) to their places in the pinned staging buffer."""
+        base = self.staging.data_ptr()
+        by_batch = {}
+        gathered, sources = [], []
+        for i in members:
+            audio = audios[i]
+            if torch.is_tensor(audio):
+                gathered.append(i)
+                sources.append(host_contiguous(audio))
+            elif audio.staged is not None:
+                gathered.append(i)
+                sources.append(audio.batch.staging[
+                    audio.staged:audio.staged + int(nbytes[i])])
+            else:
+                by_batch.setdefault(
+                    id(audio.batch), (audio.batch, []))[1].append(i)
+        for batch_files, chosen in by_batch.values():
+            batch_files.read([audios[i].index for i in chosen],
+                             where[chosen], nbytes[chosen], base)
+        if gathered:
+            host_gather(sources, nbytes[gathered], where[gathered], base,
+                        threads)
 
 
 class Staged:
@@ -351,57 +361,60 @@ class Pending:
         self.scores()
         return self._logits_dense
 
+    def _row(self, packed, counts, on_device):
+        """`Scores` of a packed word-axis row (on the device, or the lane's
+        pinned result buffer): ONE gather of the valid word columns, then
+        per-utterance views [1, W_u] of the dense row (an utterance's chunks
+        are consecutive).  No batch, no row: an empty `Scores`."""
+        if packed is None:
+            dense = torch.zeros(
+                0, device=self._lane.device if on_device else 'cpu')
+        elif packed.is_cuda:
+            # allocated on the lane's stream, consumed on the caller's: the
+            # caching allocator must not hand the block to the lane's next
+            # clone while the caller's kernels still read it
+            packed.record_stream(
+                torch.cuda.current_stream(self._lane.device))
+            columns = torch.from_numpy(self._plan.word_columns())
+            dense = packed[columns.to(packed.device)]
+            if not on_device:
+                dense = dense.cpu()
+        else:
+            # (numpy: the gather of a corpus-sized batch through torch would
+            # be a CPU parallel region, runtime.py; the fancy index copies,
+            # so the pinned buffer is free for the lane's next batch)
+            dense = torch.from_numpy(
+                packed.numpy()[self._plan.word_columns()])
+        return Scores(dense[None], counts)
+
     def scores(self):
         if self._dense is not None:
             return self._dense
-        lane, plan = self._lane, self._plan
+        lane, plan, on_device = self._lane, self._plan, self._on_device
         if plan is None or not len(plan):
-            empty = torch.zeros((1, 0))
-            if self._on_device:
-                empty = empty.to(lane.device)
-            self._dense = Scores(empty, np.zeros(self._count, dtype=np.int64))
+            counts = np.zeros(self._count, dtype=np.int64)
+            self._dense = self._row(None, counts, on_device)
             if self._want_logits:
-                self._logits_dense = Scores(
-                    empty.clone(), np.zeros(self._count, dtype=np.int64))
+                self._logits_dense = self._row(None, counts, on_device)
             return self._dense
+        counts = np.bincount(
+            plan.utterance, weights=plan.words,
+            minlength=self._count).astype(np.int64)
         with lane.lock:
             if self._dense is not None:
                 return self._dense
             lane.done.synchronize()
-            if self._on_device:
-                packed = self._scores
-                # allocated on the lane's stream, consumed on the caller's: the
-                # caching allocator must not hand the block to the lane's next
-                # clone while the caller's kernels still read it
-                packed.record_stream(torch.cuda.current_stream(lane.device))
-                columns = torch.from_numpy(plan.word_columns())
-                dense = packed[columns.to(packed.device)][None]
-            else:
-                # (numpy: the gather of a corpus-sized batch through torch would
-                # be a CPU parallel region, runtime.py; the fancy index copies,
-                # so the pinned buffer is free for the lane's next batch)
-                dense = torch.from_numpy(
-                    lane.result[:self._ld_words].numpy()[
-                        plan.word_columns()])[None]
-            logits = None
+            dense = self._row(
+                self._scores if on_device else lane.result[:self._ld_words],
+                counts, on_device)
             if self._logits is not None:
                 # (kept on the device whatever `on_device`: the same gather
                 # there, then the host copy if the scores are on the host)
-                packed = self._logits
-                packed.record_stream(torch.cuda.current_stream(lane.device))
-                columns = torch.from_numpy(plan.word_columns())
-                logits = packed[columns.to(packed.device)][None]
-                if not self._on_device:
-                    logits = logits.cpu()
+                self._logits_dense = self._row(
+                    self._logits, counts, on_device)
             if lane.pending is self:
                 lane.pending = None
-        # one gather of the valid word columns, one split: per-utterance views
-        # [1, W_u] of a dense row (an utterance's chunks are consecutive)
-        counts = np.bincount(
-            plan.utterance, weights=plan.words, minlength=self._count)
-        self._dense = Scores(dense, counts.astype(np.int64))
-        if logits is not None:
-            self._logits_dense = Scores(logits, counts.astype(np.int64))
+        self._dense = dense
         self._scores = None
         self._logits = None
         return self._dense
@@ -458,12 +471,52 @@ class Session:
         while len(self._file_buffers) < FILE_BUFFERS:
             self._file_buffers.append(None)
         slot = turn % FILE_BUFFERS
-        buffer = self._file_buffers[slot]
-        if buffer is None or buffer.numel() < nbytes:
-            buffer = torch.empty(
-                max(nbytes, 1) * 5 // 4, dtype=torch.uint8).pin_memory()
-            self._file_buffers[slot] = buffer
-        return buffer
+        self._file_buffers[slot] = grown(self._file_buffers[slot], nbytes)
+        return self._file_buffers[slot]
+
+    def _next_lane(self):
+        lane = self.lanes[self._cursor % len(self.lanes)]
+        self._cursor += 1
+        return lane
+
+    @contextlib.contextmanager
+    def _held(self, lane):
+        """`lane`, locked, with the batch it still holds finished; an enqueue
+        that raises inside leaves the lane drained and without layouts."""
+        with lane.lock:
+            if lane.pending is not None:
+                lane.pending.result()
+            try:
+                yield lane
+            except BaseException:
+                # Copies and kernels may already be queued on the lane's
+                # stream with no `done` event behind them: drain it before
+                # the pinned staging buffer can be reused, and forget the
+                # layouts (one of them may be half built / half captured).
+                try:
+                    lane.stream.synchronize()
+                except Exception:     # noqa: BLE001
+                    pass
+                lane.layouts.clear()
+                lane.pending = None
+                raise
+
+    @contextlib.contextmanager
+    def _turn(self, brief=False):
+        """THE lane turn: the next lane of the rotation, held (`_held`) - the
+        caller enqueues inside.  The session lock is held for the whole turn,
+        so submissions take their lanes, and reach their streams, in the
+        order they were made; `brief`: only while the cursor moves
+        (`resample`, which waits for its own result inside the turn and must
+        not hold up submissions to the other lanes meanwhile)."""
+        if brief:
+            with self._lock:
+                lane = self._next_lane()
+            with self._held(lane):
+                yield lane
+        else:
+            with self._lock, self._held(self._next_lane()) as lane:
+                yield lane
 
     def resample(self, audios, sample_rate, target_rate=cfg.SAMPLE_RATE,
                  on_device=False):
@@ -482,12 +535,7 @@ class Session:
         lengths = [int(audio.shape[0]) for audio in audios]
         _, orig, new, _ = load.resample_kernel(sample_rate, target_rate)
         targets = [load.resampled_length(n, orig, new) for n in lengths]
-        with self._lock:
-            lane = self.lanes[self._cursor % len(self.lanes)]
-            self._cursor += 1
-        with lane.lock:
-            if lane.pending is not None:
-                lane.pending.result()
+        with self._turn(brief=True) as lane:
             lane._reserve(max(sum(targets) * 4, sum(lengths) * 4), 1)
             if any(audio.is_cuda for audio in audios):
                 lane.stream.wait_stream(torch.cuda.current_stream(lane.device))
@@ -512,29 +560,10 @@ class Session:
         another thread): no layout cache lookup, no planning here.
         `logits`: also keep the decoder's logits (`Pending.logits()`; one
         device copy of the packed word axis, made only when asked for)."""
-        with self._lock:
-            lane = self.lanes[self._cursor % len(self.lanes)]
-            self._cursor += 1
-            with lane.lock:
-                if lane.pending is not None:
-                    lane.pending.result()
-                try:
-                    return self._enqueue(
-                        lane, list(alignments), list(audios), sample_rate,
-                        batch_size, on_device, pitch_tracker, plan,
-                        logits=logits)
-                except BaseException:
-                    # Copies and kernels may already be queued on the lane's
-                    # stream with no `done` event behind them: drain it before
-                    # the pinned staging buffer can be reused, and forget the
-                    # layouts (one of them may be half built / half captured).
-                    try:
-                        lane.stream.synchronize()
-                    except Exception:     # noqa: BLE001
-                        pass
-                    lane.layouts.clear()
-                    lane.pending = None
-                    raise
+        with self._turn() as lane:
+            return self._enqueue(
+                lane, list(alignments), list(audios), sample_rate, batch_size,
+                on_device, pitch_tracker, plan, logits=logits)
 
     def submit_staged(self, plan, staged, on_device=False):
         """`submit` of a batch that is planned (`batch.plan_batch` of its
@@ -547,57 +576,47 @@ class Session:
             raise ValueError(
                 'submit_staged: pitch / periodicity features need the samples '
                 'on the host (use submit)')
-        with self._lock:
-            lane = self.lanes[self._cursor % len(self.lanes)]
-            self._cursor += 1
-            with lane.lock:
-                if lane.pending is not None:
-                    lane.pending.result()
-                try:
-                    return self._enqueue_staged(lane, plan, staged, on_device)
-                except BaseException:
-                    try:
-                        lane.stream.synchronize()
-                    except Exception:     # noqa: BLE001
-                        pass
-                    lane.layouts.clear()
-                    lane.pending = None
-                    raise
+        nbytes = staged.lengths * load.itemsize(staged.dtype)
+        total = int(nbytes.sum())
+        with self._turn() as lane:
+            pending, live = self._open(
+                lane, plan, len(staged), on_device, False, total)
+            if not live:
+                return pending
+            with torch.cuda.device(lane.device), \
+                    torch.cuda.stream(lane.stream):
+                send_runs(lane.audio[:total], np.cumsum(nbytes) - nbytes,
+                          staged.buffer, staged.where, nbytes)
+                packed = lane.audio[:total].view(staged.dtype)
+                self._keep(lane, pending, *lane.engine.forward(packed, plan))
+            return pending
 
-    def _enqueue_staged(self, lane, plan, staged, on_device):
-        count = len(staged)
+    @staticmethod
+    def _open(lane, plan, count, on_device, logits, nbytes):
+        """What every enqueue starts with: (the batch's `Pending`, whether
+        there is anything to enqueue - then with `nbytes` of staging and the
+        plan's word axis reserved on the lane)."""
         pending = Pending(
             lane, plan, count, on_device,
-            plan.ld_words if plan is not None else 0)
+            plan.ld_words if plan is not None else 0, logits)
         if plan is None or not len(plan):
-            return pending
-        dtype = staged.dtype
-        item = 2 if dtype == torch.int16 else 4
-        offsets = np.concatenate([[0], np.cumsum(staged.lengths)])
-        total = int(offsets[-1])
-        lane._reserve(total * item, plan.ld_words)
-        # runs of utterances that lie back to back in the pinned buffer
-        nbytes = staged.lengths * item
-        cuts = np.nonzero(
-            staged.where[1:] != staged.where[:-1] + nbytes[:-1])[0] + 1
-        first = np.concatenate([[0], cuts]).tolist()
-        last = np.concatenate([cuts, [count]]).tolist()
-        with torch.cuda.device(lane.device), torch.cuda.stream(lane.stream):
-            packed = lane.audio[:max(total, 1) * item].view(dtype)[:total]
-            for lo, hi in zip(first, last):
-                start, stop = int(offsets[lo]), int(offsets[hi])
-                source = int(staged.where[lo])
-                packed[start:stop].copy_(
-                    staged.buffer[source:source + (stop - start) * item]
-                    .view(dtype), non_blocking=True)
-            scores, _ = lane.engine.forward(packed, plan)
-            if on_device:
-                pending._scores = scores.clone()
-            else:
-                lane.result[:plan.ld_words].copy_(scores, non_blocking=True)
-            lane.done.record(lane.stream)
+            return pending, False
+        lane._reserve(nbytes, plan.ld_words)
+        return pending, True
+
+    @staticmethod
+    def _keep(lane, pending, scores, word_logits):
+        """What every enqueue ends with, on the lane's stream: the scores kept
+        (a clone on the device, or a copy into the lane's pinned result), the
+        logits when asked for, the lane's `done` event behind them."""
+        if pending._want_logits:
+            pending._logits = word_logits.clone()
+        if pending._on_device:
+            pending._scores = scores.clone()
+        else:
+            lane.result[:pending._ld_words].copy_(scores, non_blocking=True)
+        lane.done.record(lane.stream)
         lane.pending = pending
-        return pending
 
     def _enqueue(self, lane, alignments, audios, sample_rate, batch_size,
                  on_device, pitch_tracker, ready=None, logits=False):
@@ -637,18 +656,15 @@ class Session:
             layout = _Layout(
                 batch.plan_batch(alignments, lengths, batch_size))
         plan = layout.plan if layout is not None else None
-        pending = Pending(
-            lane, plan, len(audios), on_device,
-            plan.ld_words if plan is not None else 0, logits)
-        if plan is None or not len(plan):
-            return pending
-        engine = lane.engine
         # (growing the buffers drops the cached layouts, whose graphs point
         # into the old ones: so before this layout joins the cache)
-        lane._reserve(
-            max(sum(lengths) * (2 if dtype == torch.int16 else 4),
-                sum(raw_lengths) * 4 if resampling else 0),
-            plan.ld_words)
+        pending, live = self._open(
+            lane, plan, len(audios), on_device, logits,
+            max(sum(lengths) * load.itemsize(dtype),
+                sum(raw_lengths) * 4 if resampling else 0))
+        if not live:
+            return pending
+        engine = lane.engine
         if fresh and key is not None:
             lane.layouts[key] = layout
             while len(lane.layouts) > _Layout.KEEP:
@@ -694,15 +710,7 @@ class Session:
             else:
                 scores, word_logits = engine.forward(
                     packed, plan, tracks=tracks)
-            if logits:
-                pending._logits = word_logits.clone()
-            if on_device:
-                pending._scores = scores.clone()
-            else:
-                lane.result[:plan.ld_words].copy_(
-                    scores, non_blocking=True)
-            lane.done.record(lane.stream)
-        lane.pending = pending
+            self._keep(lane, pending, scores, word_logits)
         return pending
 
     def run(self, alignments, audios, sample_rate=cfg.SAMPLE_RATE,
@@ -731,8 +739,8 @@ class Session:
         if len(self.lanes) < 2 or len(audios) < 2:
             return whole
         sizes = np.array(
-            [int(a.shape[-1]) * (2 if a.dtype == torch.int16 else 4)
-             for a in audios], dtype=np.int64)
+            [int(a.shape[-1]) * load.itemsize(a.dtype) for a in audios],
+            dtype=np.int64)
         total = int(sizes.sum())
         if total <= 2 * SPLIT_BYTES:
             return whole

@@ -755,7 +755,8 @@ def test_dropout_checkpoints_load():
 
 def test_host_gather_and_fork():
     """emph_host_gather (the persistent pool of copy threads behind
-    `session._Lane.stage`): pieces of any size and alignment land where they
+    `session.host_gather`, which `session._Lane.stage` fills its pinned
+    buffer with): pieces of any size and alignment land where they
     should, and a forked child - which inherits the library but not its
     worker threads - gathers with a pool of its own instead of waiting for
     the parent's."""
