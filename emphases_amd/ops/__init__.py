@@ -12,11 +12,14 @@ prefix sums, so that a caller of the reference's ATen ops
                                          cu_T, heads)                  transformer.py:18-30
     torch.ops.emphases_amd.encoder_layer_dropout(x, <the same twelve>, cu_T, heads,
                                          p, seed, stream_base, step)   the same in .train()
+    torch.ops.emphases_amd.encoder_layer_split(x, <the same twelve>, cu_T, heads,
+                                         precision)                    the plain layer, its
+                                         attention core on the bf16 matrix pipe
     torch.ops.emphases_amd.dropout(x, p, seed, stream, step)           transformer.py:51-52
     torch.ops.emphases_amd.prominence_forward(audio_packed, cu_samples, bounds, cu_words)
                                                                        core.py:295-342
 
-The package: this module holds the seven ops, their fakes and their autograd
+The package: this module holds the eight ops, their fakes and their autograd
 registrations; `layout` the prefix sums, the plans, `_Layout` and the plan LRU;
 `packs` the launch helper `_call`, `_ByStorage` and everything kept per weight;
 `layer` the launchers an op shares with its backward and `_LayerRun`.
@@ -39,8 +42,10 @@ the way to a second backward, raises) and carry a
 all twelve parameters; 80 channels in 2 heads, its dropouts the identity:
 see its docstring; `encoder_layer_dropout` is the same layer in training mode
 under the reference's four dropouts as specified masks - one body serves
-both, `dropout=None` being the plain layer - and `dropout` the
-mask alone) and `logmel` (gradient of a float `audio_packed`: the
+both, `dropout=None` being the plain layer; `encoder_layer_split` is the
+plain layer at `precision='bf16x3'`, the third caller of that body: the
+attention core of every segment of at least 128 positions on the bf16 matrix
+pipe, forward and backward - and `dropout` the mask alone) and `logmel` (gradient of a float `audio_packed`: the
 waveform end of the chain, so d(prominence)/d(audio) exists on the seams; no
 `register_fake` - its shape depends on the values of `cu_samples`);
 `prominence_forward` alone stays non-differentiable.  The backward runs on
@@ -88,16 +93,18 @@ from .. import core
 from .. import engine as engine_module
 from .. import runtime
 from .layer import (  # noqa: F401
-    LAYER_CHANNELS, LAYER_HEADS, _LayerRun, _conv1d, _weight_grad)
+    LAYER_CHANNELS, LAYER_HEADS, SPLIT_PIECES, _LayerRun, _conv1d,
+    _weight_grad)
 from .layout import (  # noqa: F401
-    DIRECT_TILE, GRAD_TILE, _Layout, _chunk_plan, _counts, _device_index,
+    DIRECT_TILE, GRAD_TILE, SPLIT_TILE, _Layout, _chunk_plan, _counts, _device_index,
     _frame_plan, _layout, _logmel_plan)
 from .packs import (  # noqa: F401
     _ByStorage, _call, _device_pack, _first, _first_versions, _float32, _host_conv,
     _layer_engine, _weight_changes, pack_index_tables)
 
 __all__ = ['logmel', 'conv1d_same_act', 'segment_reduce', 'encoder_layer',
-           'encoder_layer_dropout', 'dropout', 'prominence_forward']
+           'encoder_layer_dropout', 'encoder_layer_split', 'dropout',
+           'prominence_forward']
 
 
 @torch.library.custom_op('emphases_amd::logmel', mutates_args=())
@@ -432,22 +439,39 @@ def _layer_inputs(x, tensors, cu_T):
     return index, tuple(tensors), _layout(x.device, counts)
 
 
-def _layer_forward(x, tensors, cu_T, heads, dropout=None):
-    """The body of `encoder_layer` (`dropout` None) and of
-    `encoder_layer_dropout` (`dropout` = (p, seed, stream_base, step))."""
+def _split_pieces(precision):
+    """The `pieces` code of `precision` for `encoder_layer_split`: 'bf16x3'
+    alone.  'f32' is `encoder_layer`; the engine's other precisions raise
+    NotImplementedError, anything else ValueError (`train.check_precision`)."""
+    from ..train.core import check_precision
+    if check_precision(precision) not in SPLIT_PIECES:
+        raise ValueError(
+            f"encoder_layer_split takes precision 'bf16x3', not "
+            f'precision={precision!r}: encoder_layer is the float32 layer')
+    return SPLIT_PIECES[precision]
+
+
+def _layer_forward(x, tensors, cu_T, heads, dropout=None, precision=None):
+    """The body of `encoder_layer` (`dropout` None), of
+    `encoder_layer_dropout` (`dropout` = (p, seed, stream_base, step)) and of
+    `encoder_layer_split` (`precision`)."""
+    pieces = 0
+    if precision is not None:
+        pieces = _split_pieces(precision)
+        _check_layer_shape('encoder_layer_split', int(x.shape[0]), int(heads))
     if dropout is not None:
         _check_layer_shape('encoder_layer_dropout', int(x.shape[0]), int(heads))
         dropout = _mask_arguments(*dropout)
     index, tensors, layout = _layer_inputs(x, tensors, cu_T)
     # (the plain layer of a parameter set that never changed is the fused
     # engine's, which alone takes a `cu_T` that covers fewer columns)
-    unfused = dropout is not None or \
+    unfused = dropout is not None or pieces or \
         any([_weight_changes(tensor) for tensor in tensors])
     if unfused and layout.frame_columns.numel() != x.shape[1]:
         raise ValueError('cu_T does not cover the columns of x')
     if unfused:
         with torch.cuda.device(index):
-            run = _LayerRun(x, tensors, heads, layout, index, dropout)
+            run = _LayerRun(x, tensors, heads, layout, index, dropout, pieces)
             return run.normed2.index_select(1, layout.frame_columns)
     engine = _layer_engine(tensors, index, int(x.shape[0]), int(heads))
     plan = layout.plan
@@ -465,29 +489,41 @@ def _layer_fake(x, *rest):
     return x.new_empty(x.shape, dtype=torch.float32)
 
 
-def _layer_setup(ctx, inputs, output):
-    ctx.heads = inputs[14]
-    ctx.dropout = tuple(inputs[15:19]) or None
-    ctx.save_for_backward(*inputs[:14])
+def _layer_setup(kind):
+    """`setup_context` of the layer op `kind`: what follows `heads` in its
+    inputs is nothing ('encoder_layer'), the four mask arguments
+    ('encoder_layer_dropout') or `precision` ('encoder_layer_split')."""
+    def setup(ctx, inputs, output):
+        ctx.kind = kind
+        ctx.heads = inputs[14]
+        ctx.extra = len(inputs) - 15
+        ctx.dropout = tuple(inputs[15:19]) \
+            if kind == 'encoder_layer_dropout' else None
+        ctx.precision = inputs[15] if kind == 'encoder_layer_split' else None
+        ctx.save_for_backward(*inputs[:14])
+    return setup
 
 
 def _layer_backward(ctx, grad):
     """The thirteen gradients, and a None for every other input of the op."""
     plain = ctx.dropout is None
-    _once('encoder_layer' if plain else 'encoder_layer_dropout')
+    name = ctx.kind
+    _once(name)
     saved = ctx.saved_tensors
     x, cu_T = saved[0], saved[13]
     need = list(ctx.needs_input_grad[:13])
     _check_layer_shape(
-        'the backward of encoder_layer' if plain else 'encoder_layer_dropout',
+        'the backward of encoder_layer' if name == 'encoder_layer' else name,
         x.shape[0], ctx.heads)
-    others = (None,) * (2 if plain else 6)
+    others = (None,) * (2 + ctx.extra)          # cu_T, heads, the op's own
     if not any(need):
         return (None,) * 13 + others
     index, tensors, layout = _layer_inputs(x, saved[1:13], cu_T)
     with torch.cuda.device(index):
-        run = _LayerRun(x.detach(), tensors, ctx.heads, layout, index,
-                        None if plain else _mask_arguments(*ctx.dropout))
+        run = _LayerRun(
+            x.detach(), tensors, ctx.heads, layout, index,
+            None if plain else _mask_arguments(*ctx.dropout),
+            0 if ctx.precision is None else _split_pieces(ctx.precision))
         grads = run.backward(grad, need)
         if grads[0] is not None:
             grads[0] = grads[0].index_select(1, layout.frame_columns)
@@ -567,9 +603,46 @@ def encoder_layer_dropout(
         cu_T, heads, (p, seed, stream_base, step))
 
 
-for _op in (encoder_layer, encoder_layer_dropout):
+@torch.library.custom_op('emphases_amd::encoder_layer_split', mutates_args=())
+def encoder_layer_split(
+        x: torch.Tensor, in_proj_weight: torch.Tensor,
+        in_proj_bias: torch.Tensor, out_proj_weight: torch.Tensor,
+        out_proj_bias: torch.Tensor, norm1_weight: torch.Tensor,
+        norm1_bias: torch.Tensor, linear1_weight: torch.Tensor,
+        linear1_bias: torch.Tensor, linear2_weight: torch.Tensor,
+        linear2_bias: torch.Tensor, norm2_weight: torch.Tensor,
+        norm2_bias: torch.Tensor, cu_T: torch.Tensor, heads: int,
+        precision: str) -> torch.Tensor:
+    """`encoder_layer` at `precision='bf16x3'`: the attention core on the
+    bf16 matrix pipe, every fp32 operand split into bf16 pieces (the engine's
+    rule for attention: three pieces and six products for the scores, two and
+    three behind the softmax), fp32 accumulation.  The projections, the
+    feed-forward, the LayerNorms stay the float32 kernels; dropout is the
+    identity.
+
+    Which kernels take a segment depends on its length alone
+    (`engine.GROUPED_FROM` = 128): segments of at least 128 positions take
+    `emph_split_kv` + `emph_attention_split` and, in the backward,
+    `emph_attention_backward_split`; shorter ones `emph_attention` /
+    `emph_attention_backward` through a tile table of their own - at most two
+    launches per direction, and a batch without a long segment gives the bits
+    of `encoder_layer` on updated parameters.  Always the unfused sequence of
+    `_LayerRun`.  80 channels in 2 heads only (NotImplementedError);
+    `precision` 'bf16x3' only: 'f32' is `encoder_layer` (ValueError),
+    'bf16x3_fast' / 'bf16x6' raise NotImplementedError."""
+    return _layer_forward(
+        x, (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias,
+            norm1_weight, norm1_bias, linear1_weight, linear1_bias,
+            linear2_weight, linear2_bias, norm2_weight, norm2_bias),
+        cu_T, heads, precision=precision)
+
+
+for _kind, _op in (('encoder_layer', encoder_layer),
+                   ('encoder_layer_dropout', encoder_layer_dropout),
+                   ('encoder_layer_split', encoder_layer_split)):
     _op.register_fake(_layer_fake)
-    _op.register_autograd(_layer_backward, setup_context=_layer_setup)
+    _op.register_autograd(
+        _layer_backward, setup_context=_layer_setup(_kind))
 
 
 def _masked(x, p, seed, stream, step):

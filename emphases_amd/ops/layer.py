@@ -4,12 +4,16 @@ layer as an unfused sequence that keeps every intermediate."""
 import torch
 
 from .. import config as cfg
+from .. import engine as engine_module
 from .. import runtime
-from .layout import DIRECT_TILE, GRAD_TILE
+from .layout import DIRECT_TILE, GRAD_TILE, SPLIT_TILE
 from .packs import _call, _device_pack, _float32
 
 LAYER_CHANNELS, LAYER_HEADS = 80, 2      # emph_attention_backward
 LAYER_EPS = cfg.Config(architecture='transformer').layer_norm_eps
+# `precision` of encoder_layer_split -> the `pieces` code of emph_attention_split
+# (three pieces for the scores, two behind the softmax: engine.PRECISIONS)
+SPLIT_PIECES = {'bf16x3': 32}
 
 
 def _conv1d(x, y, ld, pack, bias, c_in, c_out, kernel_size, activation,
@@ -51,14 +55,21 @@ class _LayerRun:
     dropouts of the layer (`train/dropout.py`): `emph_attention_dropout` in
     place of `emph_attention` under stream_base, and `emph_dropout` in place
     on `projected`, `hidden` and `fed` (whole packed buffers [rows, ld]) under
-    stream_base + 1, + 2, + 3."""
+    stream_base + 1, + 2, + 3.
 
-    def __init__(self, x, tensors, heads, layout, index, dropout=None):
+    `pieces` (a code of `SPLIT_PIECES`): the attention core on the bf16
+    matrix pipe for the segments of at least `engine.GROUPED_FROM` positions
+    (`emph_split_kv` + `emph_attention_split`, `emph_attention_backward_split`);
+    shorter ones keep the fp32 kernels through a tile table of their own.  By
+    segment length alone: a segment's result does not depend on the batch."""
+
+    def __init__(self, x, tensors, heads, layout, index, dropout=None,
+                 pieces=0):
         (self.in_w, self.in_b, self.out_w, self.out_b, self.norm1_w,
          self.norm1_b, self.ff1_w, self.ff1_b, self.ff2_w, self.ff2_b,
          self.norm2_w, self.norm2_b) = tensors
         self.layout, self.index, self.heads = layout, index, int(heads)
-        self.dropout = dropout
+        self.dropout, self.pieces = dropout, int(pieces)
         self.ld = ld = layout.plan.ld_frames
         self.channels = channels = int(x.shape[0])
         self.device = x.device
@@ -122,8 +133,30 @@ class _LayerRun:
         name, tile, mask = 'emph_attention', DIRECT_TILE, (None,)
         if self.dropout is not None:
             name, tile, mask = 'emph_attention_dropout', GRAD_TILE, self.dropout
-        _call(name, self.qk, self.v, self.attended, self.ld, self.channels,
-              self.heads, self.tiles, self.n_tiles, tile, *mask)
+        tiles, n_tiles = self.tiles, self.n_tiles
+        if self.pieces:
+            tiles, n_tiles = self.layout.tiles(tile, engine_module.SHORT)
+            self.attention_split()
+        if n_tiles or not self.pieces:
+            _call(name, self.qk, self.v, self.attended, self.ld,
+                  self.channels, self.heads, tiles, n_tiles, tile, *mask)
+
+    def attention_split(self):
+        """`attended` of the long segments: their keys and values split once,
+        then the workgroup kernel on the bf16 pipe."""
+        stages, n_stages = self.layout.tiles(DIRECT_TILE, engine_module.LONG)
+        tiles, n_tiles = self.layout.tiles(SPLIT_TILE, engine_module.LONG)
+        if not n_tiles:
+            return
+        size = int(runtime.library().emph_split_kv_bytes(
+            self.ld, len(self.layout.plan), self.channels, self.heads,
+            self.pieces))
+        images = torch.empty(size, dtype=torch.uint8, device=self.device)
+        _call('emph_split_kv', self.qk, self.v, self.ld, self.channels,
+              self.heads, stages, n_stages, DIRECT_TILE, self.pieces, images)
+        _call('emph_attention_split', self.qk, images, self.attended, self.ld,
+              self.channels, self.heads, tiles, n_tiles, SPLIT_TILE, None,
+              self.pieces)
 
     def add_layernorm(self, x, r, y, gamma, beta):
         _call('emph_add_layernorm', x, r, y, self.ld, self.channels,
@@ -153,13 +186,36 @@ class _LayerRun:
         if self.dropout is not None:
             name, mask = 'emph_attention_dropout_backward', self.dropout
         dqkv = self.zeros(3 * self.channels)
-        size = getattr(runtime.library(), name + '_workspace')
-        workspace = torch.empty(max(1, int(size(self.ld, self.heads))),
-                                dtype=torch.float32, device=self.device)
-        _call(name, self.qk, self.v, self.attended, dattended, dqkv, self.ld,
-              self.channels, self.heads, self.tiles, self.n_tiles, GRAD_TILE,
-              workspace, *mask)
+        library = runtime.library()
+        sizes = [getattr(library, name + '_workspace')]
+        if self.pieces:
+            # (one buffer serves both launches: they walk other segments)
+            sizes.append(library.emph_attention_backward_split_workspace)
+        workspace = torch.empty(
+            max(1, *[int(size(self.ld, self.heads)) for size in sizes]),
+            dtype=torch.float32, device=self.device)
+        tiles, n_tiles = self.tiles, self.n_tiles
+        if self.pieces:
+            tiles, n_tiles = self.layout.tiles(GRAD_TILE, engine_module.SHORT)
+            self.attention_backward_split(dattended, dqkv, workspace)
+        if n_tiles or not self.pieces:
+            _call(name, self.qk, self.v, self.attended, dattended, dqkv,
+                  self.ld, self.channels, self.heads, tiles, n_tiles,
+                  GRAD_TILE, workspace, *mask)
         return dqkv
+
+    def attention_backward_split(self, dattended, dqkv, workspace):
+        """The long segments' columns of `dqkv` on the bf16 pipe (`workspace`:
+        at least `emph_attention_backward_split_workspace` floats)."""
+        tiles, n_tiles = self.layout.tiles(SPLIT_TILE, engine_module.LONG)
+        if not n_tiles:
+            return
+        size = int(runtime.library().emph_attention_backward_split_bytes(
+            self.ld, len(self.layout.plan), self.channels, self.heads))
+        images = torch.empty(size, dtype=torch.uint8, device=self.device)
+        _call('emph_attention_backward_split', self.qk, self.v, self.attended,
+              dattended, dqkv, self.ld, self.channels, self.heads, tiles,
+              n_tiles, SPLIT_TILE, images, workspace)
 
     def backward(self, grad, need):
         """The thirteen gradients (packed dx gathered by the caller; None

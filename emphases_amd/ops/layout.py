@@ -15,6 +15,7 @@ from .. import runtime
 
 GRAD_TILE = 64       # emph_conv_weight_grad_any, emph_segment_reduce_backward
 DIRECT_TILE = 64     # emph_conv1d of the device-packed path and of the data gradient
+SPLIT_TILE = 256     # emph_attention_split, emph_attention_backward_split
 PLAN_CACHE_SIZE = 16
 
 
@@ -96,12 +97,13 @@ class _Layout:
     def view(self, name):
         return self.meta[name][0]
 
-    def tiles(self, tile):
-        """(device tile table of the frame axis `tile` wide, its rows)."""
-        key = ('tiles', runtime.AXIS_FRAMES, tile)
+    def tiles(self, tile, select=()):
+        """(device tile table of the frame axis `tile` wide, its rows);
+        `select` = (least, most) positions: of the segments of that size."""
+        key = ('tiles', runtime.AXIS_FRAMES, tile) + tuple(select)
         if key not in self.meta:
             host = np.ascontiguousarray(
-                self.plan.tiles(runtime.AXIS_FRAMES, tile)).ravel()
+                self.plan.tiles(runtime.AXIS_FRAMES, tile, *select)).ravel()
             self.meta[key] = (
                 torch.from_numpy(host).to(self.buffer.device), host.size)
         tiles, size = self.meta[key]

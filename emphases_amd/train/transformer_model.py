@@ -21,6 +21,12 @@ model in training mode draws all five, as specified masks
 `attention_keep_mask`) of (`seed`, site, `self.steps`), through
 `ops.dropout` and `ops.encoder_layer_dropout`; in `eval()` it drops nothing.
 `Config.dropout` (the conv stacks' switch) is refused either way.
+
+Precision.  `precision='bf16x3'` routes every layer of both stacks through
+`ops.encoder_layer_split`: the attention core of every segment of at least
+128 positions (the frame axis, in practice) runs on the bf16 matrix pipe,
+forward and backward; shorter segments (the words) and everything else stay
+float32.  The default 'f32' calls exactly what it always called.
 """
 import collections
 import functools
@@ -137,9 +143,10 @@ class _Layer(torch.nn.Module):
                 weight=state[f'{prefix}{name}.weight'],
                 bias=state[f'{prefix}{name}.bias']))
 
-    def forward(self, x, cu, dropout=None):
+    def forward(self, x, cu, dropout=None, precision='f32'):
         """`dropout` = (seed, stream_base, step): the layer in training mode
-        under the reference's dropout."""
+        under the reference's dropout.  `precision` other than 'f32': the
+        plain layer through `encoder_layer_split`."""
         attention = self.self_attn
         tensors = (
             attention.in_proj_weight, attention.in_proj_bias,
@@ -147,6 +154,9 @@ class _Layer(torch.nn.Module):
             self.norm1.weight, self.norm1.bias, self.linear1.weight,
             self.linear1.bias, self.linear2.weight, self.linear2.bias,
             self.norm2.weight, self.norm2.bias)
+        if precision != 'f32':
+            return torch.ops.emphases_amd.encoder_layer_split(
+                x, *tensors, cu, HEADS, precision)
         if dropout is None:
             return torch.ops.emphases_amd.encoder_layer(x, *tensors, cu, HEADS)
         seed, stream_base, step = dropout
@@ -173,8 +183,9 @@ class _Transformer(torch.nn.Module):
     """`Transformer` (`transformer.py:13-30`): x + encoding[position in the
     segment], then the layers (`model.layers.<i>`)."""
 
-    def __init__(self, config, prefix, state):
+    def __init__(self, config, prefix, state, precision='f32'):
         super().__init__()
+        self.precision = precision
         self.streams = (
             spec.transformer_stream(config, prefix),
             [spec.transformer_stream(config, prefix, i, 'attention')
@@ -196,7 +207,7 @@ class _Transformer(torch.nn.Module):
         x = x + self.encoding.index_select(1, index)
         if dropout is None:
             for layer in self.model.layers:
-                x = layer(x, cu)
+                x = layer(x, cu, precision=self.precision)
             return x
         seed, step = dropout
         position, layers = self.streams
@@ -209,7 +220,7 @@ class _Transformer(torch.nn.Module):
 
 class TransformerModel(torch.nn.Module):
     """`TransformerModel(config, checkpoint=None, seed=0,
-    reference_dropout=False)`; `forward(features
+    reference_dropout=False, precision='f32')`; `forward(features
     [C_in, sum T], cu_frames, bounds [2, sum W], cu_words) -> logits [sum W]`,
     the utterances back to back (`cu_*`: N + 1 prefix sums, on the host), as
     `TorchModel`; `train.loss_fn` serves unchanged.
@@ -221,6 +232,12 @@ class TransformerModel(torch.nn.Module):
     parameter, not in `state_dict()`) that the caller sets or advances once
     per optimizer update, so the same batch at the same `steps` gives the
     same bits.  In `eval()`, and with the default False, nothing is dropped.
+    `precision='bf16x3'` (module docstring; `train.check_precision` names the
+    others) trains and infers with the long segments' attention on the bf16
+    matrix pipe; `train()` and `eval()` compute the same function, the
+    checkpoints do not record it and are interchangeable with 'f32'; with
+    `reference_dropout=True` it raises NotImplementedError (the masked
+    kernels are float32).
     The parameters carry
     the reference's names and order (`weights.parameter_shapes`):
     `state_dict()` is read by `weights.load` and by every inference entry
@@ -229,11 +246,18 @@ class TransformerModel(torch.nn.Module):
     5000-entry positional encoding raises ValueError."""
 
     def __init__(self, config=None, checkpoint=None, seed=0,
-                 reference_dropout=False):
+                 reference_dropout=False, precision='f32'):
         super().__init__()
+        from .core import check_precision
         self.config = config = config or api.active_config()
         check_transformer_supported(config)
+        self.precision = check_precision(precision)
         self.reference_dropout = bool(reference_dropout)
+        if self.reference_dropout and self.precision != 'f32':
+            raise NotImplementedError(
+                'TransformerModel supports reference_dropout=True at '
+                f"precision 'f32' only, not precision={precision!r}: the "
+                'masked attention kernels are float32')
         self.seed, self.steps = int(seed), 0
         if checkpoint is None:
             state = initial_transformer_state(config, seed)
@@ -241,9 +265,11 @@ class TransformerModel(torch.nn.Module):
             state = weights_module.load(checkpoint, config)
         self.input_layer = _Parameters(
             weight=state['input_layer.weight'], bias=state['input_layer.bias'])
-        self.frame_encoder = _Transformer(config, 'frame_encoder', state)
+        self.frame_encoder = _Transformer(
+            config, 'frame_encoder', state, self.precision)
         if config.has_decoder:
-            self.word_decoder = _Transformer(config, 'word_decoder', state)
+            self.word_decoder = _Transformer(
+                config, 'word_decoder', state, self.precision)
         self.output_layer = _Parameters(
             weight=state['output_layer.weight'],
             bias=state['output_layer.bias'])

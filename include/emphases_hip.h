@@ -1568,6 +1568,45 @@ int emph_attention_backward(const float* qk, const float* v, const float* out,
                             int32_t heads, const int32_t* tiles, int32_t n_tiles,
                             int32_t tile_n, float* workspace, void* stream);
 
+/* emph_attention_backward on the bf16 matrix pipe, for the segments the split
+ * forward takes (emph_split_kv + emph_attention_split, `pieces` 32): the
+ * engine's 'bf16x3' rule for attention.  Every fp32 operand is split into bf16
+ * pieces rounded to nearest; the scores S = Q K^T / sqrt(d) take THREE pieces
+ * per operand and six products (their error sits in front of an exponential),
+ * the four products behind the softmax - dO V^T, P^T dO, dS K, dS^T Q - TWO
+ * pieces and three products, P and dS split as fp32 values where they stand
+ * in the accumulators.  Accumulation, the row log-sum-exp, D and
+ * dS = P o (dP - D) stay fp32.
+ *   qk, v, out, dout, dqkv  as emph_attention_backward takes and leaves them
+ *   tiles      the 256-wide tile table of the segments to cover (tile_n = 256;
+ *              the caller's choice - the ops take those of at least 128
+ *              positions, `Plan.tiles(axis, 256, 128, most)`); any length >= 1
+ *   images     emph_attention_backward_split_bytes(ld, n_segments, channels,
+ *              heads) bytes, 16-byte aligned, n_segments = ALL segments of the
+ *              packed axis (a stage's slot is offset / 64 + segment + stage):
+ *              scratch for the split operands, 92 928 bytes per 64 positions
+ *              and head (-1: a shape the kernels do not take)
+ *   workspace  emph_attention_backward_split_workspace(ld, heads) floats: the
+ *              row log-sum-exp (log2 units) and D, [2][heads][ld]
+ * Three launches: the images (Q, K, V, dO split once per 64 positions, laid
+ * out as the MFMA fragments read them), a pass per 256 queries (log-sum-exp
+ * and D into the workspace, then dQ) and a pass per 256 keys (dK, dV), the
+ * images staged through LDS 64 positions at a time.  No atomics: every element
+ * of dqkv inside a covered segment is written by one lane in a fixed order, so
+ * the same inputs give the same bits, and a segment's result does not depend
+ * on what else is in the batch.  Columns outside the covered segments are
+ * neither read nor written.  Only channels 80 in 2 heads and ld < 2^28 (tile
+ * offsets are int32; the limit of the fp32 kernels beside it); anything else
+ * returns EMPH_ERANGE and launches nothing. */
+int64_t emph_attention_backward_split_workspace(int64_t ld, int32_t heads);
+int64_t emph_attention_backward_split_bytes(int64_t ld, int32_t n_segments, int32_t channels,
+                                            int32_t heads);
+int emph_attention_backward_split(const float* qk, const float* v, const float* out,
+                                  const float* dout, float* dqkv, int64_t ld, int32_t channels,
+                                  int32_t heads, const int32_t* tiles, int32_t n_tiles,
+                                  int32_t tile_n, void* images, float* workspace,
+                                  void* stream);
+
 /* The attention of TRAINING: emph_attention with key_counts == NULL and the
  * dropout of nn.MultiheadAttention on the softmax weights
  * (transformer.py:18-23 keeps torch's default dropout = 0.1):

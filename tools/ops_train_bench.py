@@ -5,6 +5,10 @@ PyTorch and against the fused trainer.
     python tools/ops_train_bench.py --architecture transformer \
         [--out profiles/ops_transformer_train_step.json] \
         [--kernels-out profiles/attention_backward_kernels.json]
+    python tools/ops_train_bench.py --architecture transformer --precision bf16x3 \
+        [--parent <checkout of the parent commit, built>] \
+        [--out profiles/ops_transformer_train_step_bf16x3.json] \
+        [--kernels-out profiles/attention_backward_split_kernels.json]
 
 The batch and the baselines are `tools/train_bench.py`'s: 75 utterances x
 1 000 frames x 30 words, default configuration, weights of `emphases.Model()`
@@ -42,6 +46,18 @@ without dropout (the code path every earlier figure was taken on), and
 positional dropout of 0.1 under autograd and Adam in float32.  `--kernels-out`
 then also times `emph_attention_dropout` and the two passes of
 `emph_attention_dropout_backward` (p = 0.1) beside the plain kernels.
+
+`--precision bf16x3` (with `--architecture transformer`): `ops_bf16x3`, the
+step of `TransformerModel(precision='bf16x3')`, in the same alternation as
+`ops` (the f32 model of this checkout) and `torch_fp32`.  `--parent
+DIRECTORY` (with `--architecture transformer`, at either precision) adds
+`ops_parent`, the f32 step of the package of that checkout in a child process
+(this file's `--serve`), lap for lap between the others.
+`--kernels-out` then times the split launches - `emph_split_kv` +
+`emph_attention_split` and the three launches of
+`emph_attention_backward_split` - beside `emph_attention` and
+`emph_attention_backward` in the same run, with the MFMA flops they execute
+over the bf16 peak.
 """
 import argparse
 import json
@@ -61,6 +77,7 @@ from emphases_amd import train  # noqa: E402
 
 
 PEAK_FP32_MFMA = 157.3e12
+PEAK_BF16_MFMA = 16 * PEAK_FP32_MFMA      # the bf16 matrix rate
 
 
 class TorchTransformer(torch.nn.Module):
@@ -228,6 +245,168 @@ def attention_kernels(path, items, frames, dropout=False):
         file.write('\n')
 
 
+def split_kernels(path, items, frames):
+    """Per-kernel times of the split forward and of the three launches of
+    `emph_attention_backward_split` on one layer's shapes, beside
+    `emph_attention` and `emph_attention_backward` in the same run."""
+    from emphases_amd import engine, ops, runtime
+    device = torch.device('cuda', 0)
+    layout = ops._layout(device, np.full(items, frames, dtype=np.int64))
+    ld = layout.plan.ld_frames
+    tiles, n_tiles = layout.tiles(64)
+    stages, n_stages = layout.tiles(64, engine.LONG)
+    groups, n_groups = layout.tiles(256, engine.LONG)
+    generator = torch.Generator(device='cuda').manual_seed(0)
+    qk = torch.randn(160, ld, device=device, generator=generator)
+    v = torch.randn(ld, 80, device=device, generator=generator)
+    dout = torch.randn(80, ld, device=device, generator=generator)
+    out = torch.zeros(80, ld, device=device)
+    dqkv = torch.zeros(240, ld, device=device)
+    lib = runtime.library()
+    workspace = torch.empty(
+        int(lib.emph_attention_backward_workspace(ld, 2)), device=device)
+    forward_images = torch.empty(
+        int(lib.emph_split_kv_bytes(ld, items, 80, 2, 32)),
+        dtype=torch.uint8, device=device)
+    images = torch.empty(
+        int(lib.emph_attention_backward_split_bytes(ld, items, 80, 2)),
+        dtype=torch.uint8, device=device)
+    names = ('emph_attention', 'backward_queries', 'backward_keys',
+             'emph_split_kv', 'emph_attention_split', 'split_backward_images',
+             'split_backward_queries', 'split_backward_keys')
+    times = {name: [] for name in names}
+    for lap in range(8):
+        with runtime.LaunchTimer() as timer:
+            runtime.check(lib.emph_attention(
+                qk.data_ptr(), v.data_ptr(), out.data_ptr(), ld, 80, 2,
+                tiles.data_ptr(), n_tiles, 64, None, runtime.stream()),
+                'emph_attention')
+            runtime.check(lib.emph_attention_backward(
+                qk.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                dqkv.data_ptr(), ld, 80, 2, tiles.data_ptr(), n_tiles, 64,
+                workspace.data_ptr(), runtime.stream()),
+                'emph_attention_backward')
+            runtime.check(lib.emph_split_kv(
+                qk.data_ptr(), v.data_ptr(), ld, 80, 2, stages.data_ptr(),
+                n_stages, 64, 32, forward_images.data_ptr(),
+                runtime.stream()), 'emph_split_kv')
+            runtime.check(lib.emph_attention_split(
+                qk.data_ptr(), forward_images.data_ptr(), out.data_ptr(), ld,
+                80, 2, groups.data_ptr(), n_groups, 256, None, 32,
+                runtime.stream()), 'emph_attention_split')
+            runtime.check(lib.emph_attention_backward_split(
+                qk.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                dqkv.data_ptr(), ld, 80, 2, groups.data_ptr(), n_groups, 256,
+                images.data_ptr(), workspace.data_ptr(), runtime.stream()),
+                'emph_attention_backward_split')
+        assert timer.launches == len(names), timer.launches
+        if lap:                                     # (the first lap warms up)
+            for name, value in zip(names, timer.microseconds):
+                times[name].append(float(value))
+    # executed flops.  fp32: 16 x 16 score blocks of 16x16x4 instructions
+    # (attention_kernels); bf16: 32 x 32 score blocks of 32x32x16 ones - the
+    # query pass 18 (scores) + 18 + 9 + 12 (scores, dP, dQ in two m-tiles of
+    # which the second holds 8 rows of 32), the key pass 18 + 9 + 12 + 12
+    small = items * 2 * ((frames + 15) // 16) ** 2
+    large = items * 2 * ((frames + 31) // 32) ** 2
+    mfma4, mfma16 = 2 * 16 * 16 * 4, 2 * 32 * 32 * 16
+    flops = {'emph_attention': small * 22 * mfma4,
+             'backward_queries': small * (10 + 20 + 12) * mfma4,
+             'backward_keys': small * (20 + 24) * mfma4,
+             'split_backward_queries': large * (18 + 18 + 9 + 12) * mfma16,
+             'split_backward_keys': large * (18 + 9 + 12 + 12) * mfma16}
+    record = {'shape': {'utterances': items, 'positions': frames, 'heads': 2,
+                        'head_dimension': 40},
+              'device': torch.cuda.get_device_name(0), 'kernels': {}}
+    kernels = record['kernels']
+    for name, values in times.items():
+        kernels[name] = {'us_median': float(np.median(values)),
+                         'us_laps': values}
+        if name in flops:
+            bf16 = name.startswith('split_')
+            kernels[name]['executed_mfma_flops'] = flops[name]
+            kernels[name]['fraction_of_bf16_mfma_peak' if bf16 else
+                          'fraction_of_fp32_mfma_peak'] = \
+                flops[name] / (kernels[name]['us_median'] * 1e-6) / (
+                    PEAK_BF16_MFMA if bf16 else PEAK_FP32_MFMA)
+
+    def together(parts, peak, label):
+        total = {'us_median': sum(kernels[p]['us_median'] for p in parts)}
+        if all(p in flops for p in parts if 'images' not in p):
+            total['executed_mfma_flops'] = sum(flops.get(p, 0) for p in parts)
+            total[label] = total['executed_mfma_flops'] / (
+                total['us_median'] * 1e-6) / peak
+        return total
+    kernels['emph_attention_backward'] = together(
+        ('backward_queries', 'backward_keys'), PEAK_FP32_MFMA,
+        'fraction_of_fp32_mfma_peak')
+    kernels['emph_attention_backward_split'] = together(
+        ('split_backward_images', 'split_backward_queries',
+         'split_backward_keys'), PEAK_BF16_MFMA, 'fraction_of_bf16_mfma_peak')
+    kernels['split_forward'] = {'us_median': sum(
+        kernels[p]['us_median']
+        for p in ('emph_split_kv', 'emph_attention_split'))}
+    record['backward_split_over_backward'] = \
+        kernels['emph_attention_backward_split']['us_median'] / \
+        kernels['emph_attention_backward']['us_median']
+    print(json.dumps(record))
+    with open(path, 'w') as file:
+        json.dump(record, file, indent=1)
+        file.write('\n')
+
+
+def transformer_step(config, state, precision=None):
+    """(the model, its step on the bench batch): forward + backward + Adam."""
+    batch = train_bench.make_batch()
+    features, _, bounds, _, targets = batch
+    items, frames, words = \
+        train_bench.ITEMS, train_bench.FRAMES, train_bench.WORDS
+    keywords = {} if precision is None else {'precision': precision}
+    model = train.TransformerModel(config, checkpoint=state, **keywords).cuda()
+    optimizer = torch.optim.Adam(model.parameters())
+    flat = (features.permute(1, 0, 2).reshape(80, items * frames).cuda(),
+            torch.arange(items + 1) * frames,
+            bounds.permute(1, 0, 2).reshape(2, items * words),
+            torch.arange(items + 1) * words)
+    flat_targets = targets.reshape(items * words).cuda()
+
+    def step():
+        optimizer.zero_grad(set_to_none=True)
+        loss = train.loss_fn(model(*flat), flat_targets, 'bce')
+        loss.backward()
+        optimizer.step()
+        return loss.detach()
+    return model, step
+
+
+class Parent(train_bench.Parent):
+    """The f32 Transformer step of another checkout of this package in a
+    child process: this file's `--serve` on that checkout's package."""
+
+    def __init__(self, directory):
+        import subprocess
+        directory = os.path.abspath(directory)
+        self.process = subprocess.Popen(
+            [sys.executable, os.path.abspath(__file__), '--serve'],
+            cwd=directory, env=dict(os.environ, EMPHASES_BENCH_ROOT=directory),
+            stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+
+
+def serve():
+    """The child of `Parent`: 0 -> one step, its loss; n -> a timed lap.
+    (No `precision=`: the package may be older than the keyword.)"""
+    torch.cuda.set_device(0)
+    config = emphases_amd.Config(architecture='transformer', layers=6)
+    state = train.initial_transformer_state(config, seed=0)
+    _, step = transformer_step(config, state)
+    for line in sys.stdin:
+        steps = int(line)
+        if steps == 0:
+            print(float(step()), flush=True)
+        else:
+            print(train_bench.timed(step, steps), flush=True)
+
+
 def transformer_main(arguments):
     torch.cuda.set_device(0)
     batch = train_bench.make_batch()
@@ -264,6 +443,11 @@ def transformer_main(arguments):
         'torch_fp32': lambda: train_bench.torch_step(
             plain, plain_optimizer, None, device_features, membership,
             device_targets)}
+    if arguments.precision != 'f32':
+        _, split_step = transformer_step(config, state, arguments.precision)
+        contenders = {f'ops_{arguments.precision}': split_step, **contenders}
+    if arguments.parent:
+        contenders['ops_parent'] = Parent(arguments.parent)
     if arguments.reference_dropout:
         dropping = train.TransformerModel(
             config, checkpoint=state, reference_dropout=True).cuda()
@@ -289,19 +473,23 @@ def transformer_main(arguments):
                 device_targets)}
     first = {}
     for name, function in contenders.items():
-        first[name] = float(function().detach())
+        loss = function()
+        first[name] = float(loss.detach() if torch.is_tensor(loss) else loss)
         for _ in range(2):
             function()
     torch.cuda.synchronize()
     steps = {}
     for name, function in contenders.items():
-        probe = train_bench.timed(function, 2)
+        probe = train_bench.run_lap(function, 2)
         steps[name] = arguments.steps or max(
             2, int(arguments.seconds * 1e3 / probe))
     laps = {name: [] for name in contenders}
     for _ in range(arguments.laps):
         for name, function in contenders.items():
-            laps[name].append(train_bench.timed(function, steps[name]))
+            laps[name].append(train_bench.run_lap(function, steps[name]))
+    for function in contenders.values():
+        if isinstance(function, train_bench.Parent):
+            function.close()
     record = {
         'architecture': 'transformer', 'layers': config.layers,
         'downsample_location': config.downsample_location,
@@ -320,12 +508,26 @@ def transformer_main(arguments):
             median['torch_fp32_dropout'] / median['ops_dropout']
     else:
         record['torch_fp32_over_ops'] = median['torch_fp32'] / median['ops']
+    if arguments.precision != 'f32':
+        name = f'ops_{arguments.precision}'
+        record['precision'] = arguments.precision
+        record[f'ops_over_{name}'] = median['ops'] / median[name]
+        record[f'slowest_{name}_lap_below_fastest_ops_lap'] = bool(
+            max(laps[name]) < min(laps['ops']))
+    if 'ops_parent' in laps:
+        # (no regression: the f32 step of this checkout is not above the
+        # parent's laps; below them is no regression either)
+        record['ops_over_ops_parent'] = median['ops'] / median['ops_parent']
+        record['ops_at_or_below_the_parents_slowest_lap'] = bool(
+            median['ops'] <= max(laps['ops_parent']))
     print(json.dumps(record))
     if arguments.out:
         with open(arguments.out, 'w') as file:
             json.dump(record, file, indent=1)
             file.write('\n')
-    if arguments.kernels_out:
+    if arguments.kernels_out and arguments.precision != 'f32':
+        split_kernels(arguments.kernels_out, items, frames)
+    elif arguments.kernels_out:
         attention_kernels(arguments.kernels_out, items, frames,
                           arguments.reference_dropout)
 
@@ -336,11 +538,28 @@ def main():
                         choices=('convolution', 'transformer'))
     parser.add_argument('--kernels-out', default=None)
     parser.add_argument('--reference_dropout', action='store_true')
+    parser.add_argument('--precision', default='f32',
+                        choices=('f32', 'bf16x3'))
+    parser.add_argument('--parent', default=None)
+    parser.add_argument('--serve', action='store_true')
     parser.add_argument('--laps', type=int, default=7)
     parser.add_argument('--seconds', type=float, default=1.0)
     parser.add_argument('--steps', type=int, default=None)
     parser.add_argument('--out', default=None)
     arguments = parser.parse_args()
+    if arguments.serve:
+        return serve()
+    if arguments.precision != 'f32' and (
+            arguments.architecture != 'transformer' or
+            arguments.reference_dropout):
+        parser.error('--precision bf16x3 goes with --architecture '
+                     'transformer, without --reference_dropout '
+                     '(tools/train_bench.py --precision times the conv step)')
+    if arguments.parent and (arguments.architecture != 'transformer' or
+                             arguments.reference_dropout):
+        parser.error('--parent goes with --architecture transformer, '
+                     'without --reference_dropout (tools/train_bench.py '
+                     '--parent times the conv steps of a parent checkout)')
     if arguments.architecture == 'transformer':
         return transformer_main(arguments)
     torch.cuda.set_device(0)
