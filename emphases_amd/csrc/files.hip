@@ -116,19 +116,17 @@ class Workers {
             Task* task = nullptr;
             {
                 std::unique_lock<std::mutex> lock(mutex_);
+                // (the task is chosen where it is found: `next` moves without the
+                // mutex, in drain(), so a second look may find no task any more)
                 wake_.wait(lock, [&] {
                     for (Task* candidate : queue_)
                         if (candidate->next.load() < candidate->count &&
-                            candidate->inside < candidate->helpers)
+                            candidate->inside < candidate->helpers) {
+                            task = candidate;
                             return true;
+                        }
                     return false;
                 });
-                for (Task* candidate : queue_)
-                    if (candidate->next.load() < candidate->count &&
-                        candidate->inside < candidate->helpers) {
-                        task = candidate;
-                        break;
-                    }
                 ++task->inside;
             }
             drain(*task);

@@ -121,20 +121,73 @@ __global__ __launch_bounds__(256) void segment_broadcast_kernel(
 // _single_tensor_adam): lerp, mul + addcmul, sqrt / sqrt(bc2) + eps, addcdiv.
 // weight1 = 1 - beta1 and weight2 = 1 - beta2 are formed in double and rounded
 // once, as torch's Python scalars are: 1.f - 0.999f is 2e-6 off 0.001f.
+struct AdamScalars {
+    float weight1, beta2, weight2, step_size, correction2_sqrt, eps;
+};
+
+// The update of ONE element: what both kernels below evaluate, so that they
+// give the same bits.  Which products the compiler fuses into their sums is
+// its choice per kernel (it fused only the last line of adam_step_kernel when
+// that held these expressions itself, and the second line as well once they
+// were inlined), so the choice is written down: contraction off, and the one
+// fused multiply-add spelled out.  These are the roundings adam_step_kernel
+// always had.
+__device__ __forceinline__ void adam_update(float* __restrict__ parameter, float g,
+                                            float* __restrict__ exp_avg,
+                                            float* __restrict__ exp_avg_sq, int64_t i,
+                                            const AdamScalars& s) {
+#pragma clang fp contract(off)
+    const float m = exp_avg[i] + s.weight1 * (g - exp_avg[i]);
+    const float v = exp_avg_sq[i] * s.beta2 + s.weight2 * g * g;
+    exp_avg[i] = m;
+    exp_avg_sq[i] = v;
+    const float denominator = sqrtf(v) / s.correction2_sqrt + s.eps;
+    parameter[i] = fmaf(-s.step_size, m / denominator, parameter[i]);
+}
+
 __global__ __launch_bounds__(256) void adam_step_kernel(
     float* __restrict__ parameter, const float* __restrict__ gradient,
     float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, int64_t count,
-    float weight1, float beta2, float weight2, float step_size, float correction2_sqrt,
-    float eps) {
+    AdamScalars scalars) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= count) return;
-    const float g = gradient[i];
-    const float m = exp_avg[i] + weight1 * (g - exp_avg[i]);
-    const float v = exp_avg_sq[i] * beta2 + weight2 * g * g;
-    exp_avg[i] = m;
-    exp_avg_sq[i] = v;
-    const float denominator = sqrtf(v) / correction2_sqrt + eps;
-    parameter[i] = parameter[i] - step_size * (m / denominator);
+    adam_update(parameter, gradient[i], exp_avg, exp_avg_sq, i, scalars);
+}
+
+// The same update with the gradients where autograd left them: one tensor per
+// parameter, each anywhere.  A launch carries a table of up to kAdamTable
+// tensors in its arguments (2.3 KB of the 4 KB a launch may pass): the
+// gradient's address, the tensor's first element in the flat buffers, its
+// count, and the prefix sums of the tensors' workgroup counts.  A workgroup
+// finds its tensor by bisection over that prefix - the same for every lane,
+// so scalar loads of the arguments - and then is adam_step_kernel's workgroup
+// on that tensor: 256 consecutive elements, plain 4-byte loads and stores
+// (a gradient is aligned to its element and to nothing more).
+constexpr int kAdamTable = EMPH_ADAM_TABLE;
+
+struct AdamTable {
+    const float* gradient[kAdamTable];
+    int64_t offset[kAdamTable];
+    int32_t count[kAdamTable];
+    int32_t first_block[kAdamTable + 1];   // first_block[tensors] = the grid
+    int32_t tensors;
+};
+
+__global__ __launch_bounds__(256) void adam_step_gathered_kernel(
+    float* __restrict__ parameter, float* __restrict__ exp_avg,
+    float* __restrict__ exp_avg_sq, AdamTable table, AdamScalars scalars) {
+    const int block = static_cast<int>(blockIdx.x);
+    // the last tensor whose first workgroup is <= block (no tensor is empty,
+    // so first_block is strictly increasing)
+    int low = 0, high = table.tensors - 1;
+    while (low < high) {
+        const int middle = (low + high + 1) >> 1;
+        if (table.first_block[middle] <= block) low = middle; else high = middle - 1;
+    }
+    const int local = (block - table.first_block[low]) * 256 + static_cast<int>(threadIdx.x);
+    if (local >= table.count[low]) return;
+    const float g = table.gradient[low][local];
+    adam_update(parameter, g, exp_avg, exp_avg_sq, table.offset[low] + local, scalars);
 }
 
 }  // namespace emph
@@ -230,9 +283,62 @@ int emph_adam_step(float* parameter, const float* gradient, float* exp_avg,
                  "emph_adam_step: count out of range");
     EMPH_LAUNCH(adam_step_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256),
                 0, static_cast<hipStream_t>(stream), parameter, gradient, exp_avg, exp_avg_sq,
-                count, static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
-                static_cast<float>(1.0 - beta2), step_size, correction2_sqrt, eps);
+                count,
+                AdamScalars{static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
+                            static_cast<float>(1.0 - beta2), step_size, correction2_sqrt, eps});
     return check_launch("emph_adam_step");
+}
+
+int emph_adam_step_gathered(float* parameters, const float* const* gradients,
+                            const int64_t* offsets, const int64_t* counts, int32_t tensors,
+                            float* exp_avg, float* exp_avg_sq, double beta1, double beta2,
+                            float step_size, float correction2_sqrt, float eps, void* stream) {
+    if (tensors == 0) return EMPH_OK;
+    EMPH_REQUIRE(tensors > 0, EMPH_EINVAL, "emph_adam_step_gathered: %d tensors", tensors);
+    EMPH_REQUIRE(parameters && gradients && offsets && counts && exp_avg && exp_avg_sq,
+                 EMPH_EINVAL, "emph_adam_step_gathered: null pointer");
+    // every tensor is checked before the first launch: a refusal updates nothing
+    for (int32_t t = 0; t < tensors; ++t) {
+        EMPH_REQUIRE(counts[t] >= 0 && offsets[t] >= 0, EMPH_EINVAL,
+                     "emph_adam_step_gathered: tensor %d: negative count or offset", t);
+        EMPH_REQUIRE(counts[t] < (int64_t{1} << 30) && offsets[t] < (int64_t{1} << 39),
+                     EMPH_ERANGE, "emph_adam_step_gathered: tensor %d: count or offset out of range",
+                     t);
+        EMPH_REQUIRE(counts[t] == 0 || gradients[t], EMPH_EINVAL,
+                     "emph_adam_step_gathered: tensor %d: null gradient", t);
+        EMPH_REQUIRE(counts[t] == 0 || (reinterpret_cast<uintptr_t>(gradients[t]) & 3) == 0,
+                     EMPH_EINVAL,
+                     "emph_adam_step_gathered: tensor %d: gradient not 4-byte aligned", t);
+    }
+    const AdamScalars scalars{static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
+                              static_cast<float>(1.0 - beta2), step_size, correction2_sqrt, eps};
+    AdamTable table;
+    table.tensors = 0;
+    table.first_block[0] = 0;
+    for (int32_t t = 0; t <= tensors; ++t) {
+        if (t < tensors && counts[t] == 0) continue;   // (takes no place in a table)
+        // a launch when the next tensor finds the table full (of workgroups too), and
+        // after the last tensor
+        const int64_t blocks = t < tensors ? (counts[t] + 255) / 256 : 0;
+        const bool full = table.tensors == kAdamTable ||
+                          table.first_block[table.tensors] + blocks > (int64_t{1} << 30);
+        if ((t == tensors || full) && table.tensors > 0) {
+            EMPH_LAUNCH(adam_step_gathered_kernel,
+                        dim3(static_cast<unsigned>(table.first_block[table.tensors])), dim3(256),
+                        0, static_cast<hipStream_t>(stream), parameters, exp_avg, exp_avg_sq,
+                        table, scalars);
+            const int status = check_launch("emph_adam_step_gathered");
+            if (status != EMPH_OK) return status;
+            table.tensors = 0;
+        }
+        if (t == tensors) break;
+        const int slot = table.tensors++;
+        table.gradient[slot] = gradients[t];
+        table.offset[slot] = offsets[t];
+        table.count[slot] = static_cast<int32_t>(counts[t]);
+        table.first_block[slot + 1] = table.first_block[slot] + static_cast<int32_t>(blocks);
+    }
+    return EMPH_OK;
 }
 
 }  // extern "C"

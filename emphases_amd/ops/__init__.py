@@ -100,7 +100,7 @@ from .layout import (  # noqa: F401
     _frame_plan, _layout, _logmel_plan)
 from .packs import (  # noqa: F401
     _ByStorage, _call, _device_pack, _first, _first_versions, _float32, _host_conv,
-    _layer_engine, _weight_changes, pack_index_tables)
+    _layer_engine, _weight_changes, mark_trained, pack_index_tables)
 
 __all__ = ['logmel', 'conv1d_same_act', 'segment_reduce', 'encoder_layer',
            'encoder_layer_dropout', 'encoder_layer_split', 'dropout',

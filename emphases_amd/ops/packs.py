@@ -184,6 +184,28 @@ def _weight_changes(weight):
     return _first(weight).version != weight._version
 
 
+def mark_trained(tensors, base=None):
+    """Tells the ops that `tensors` are weights in training although their
+    versions have not moved yet - those of a trainer restored from a
+    checkpoint, whose first forward must take the path its later ones take.
+    Every tensor is shown to `_first` as an op will see it (the same address,
+    shape, strides and storage); then its version is advanced once, or -
+    `base`: a tensor whose counter all of them share as its views - that of
+    `base` alone.  Nothing is launched.  RuntimeError where a tensor still
+    looks untouched afterwards: it does not share `base`'s counter, or the
+    tensors outgrow the cache of first versions (256 entries, shared with
+    every other weight the ops have seen in the process)."""
+    for tensor in tensors:
+        _first(tensor)
+    for tensor in (tensors if base is None else [base]):
+        torch.autograd.graph.increment_version(tensor)
+    changed = all([_weight_changes(tensor) for tensor in tensors])
+    if not changed:
+        raise RuntimeError(
+            'mark_trained: a tensor does not share the version counter that '
+            'was advanced, or the weights outgrow the cache of first versions')
+
+
 def _host_conv(first, weight, bias, index):
     """`engine._Conv` of a weight that never changed (its packs made once on
     the host), kept per (weight, bias, versions, device).  `first` =

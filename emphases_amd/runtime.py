@@ -37,6 +37,7 @@ SPREAD_IDENTITY, SPREAD_LOG2 = 0, 1
 (METRIC_COUNT, METRIC_BCE, METRIC_SQUARED_ERROR, METRIC_COVARIANCE,
  METRIC_SUM_PREDICTED, METRIC_SUMSQ_PREDICTED, METRIC_SUM_TARGET,
  METRIC_SUMSQ_TARGET, METRIC_FIELDS) = range(9)
+ADAM_TABLE = 96     # EMPH_ADAM_TABLE: tensors per launch of emph_adam_step_gathered
 
 _c = ctypes
 _ptr, _i32, _i64, _f32 = _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_float
@@ -287,6 +288,9 @@ SIGNATURES = {
     'emph_adam_step': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _i64, _c.c_double, _c.c_double, _f32, _f32,
         _f32, _ptr]),
+    'emph_adam_step_gathered': (_c.c_int, [
+        _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _c.c_double, _c.c_double,
+        _f32, _f32, _f32, _ptr]),
 }
 
 _library = None

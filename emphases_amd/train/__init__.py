@@ -1,11 +1,14 @@
-"""Training the convolution model on the GPU (`emphases.train`): the step -
+"""Training on the GPU (`emphases.train`): the step of the convolution model -
 forward with every layer kept, masked loss, backward and Adam
 (`emphases/train/core.py:91-142`) - and the loop around it - resume, train,
 validate, save (`train/core.py:13-307`) - fed by `emphases_amd.data`; and
 `TorchModel`, the same architecture as a `torch.nn.Module` on the
 differentiable operator seams for the configurations the fused steps refuse.
-`TransformerModel` is the Transformer architecture on the same seams (the
-fused steps, `make_trainer` and `train` refuse it).
+`TransformerModel` is the Transformer architecture on the same seams, and
+`TransformerTrainer` the step around it with the fused steps' interface: the
+fused steps and their dispatch (`step_class` ... `make_trainer`) refuse the
+architecture, and so does `train` unless it is given
+`trainer=TransformerTrainer`.
 
 The fused steps, one class per `downsample_location` and one behind them:
 `Trainer` ('intermediate'), `EncoderTrainer` ('inference' and 'loss', no word
@@ -27,4 +30,5 @@ from .model import (  # noqa: F401
     TorchModel, check_model_supported, initial_model_state, loss_fn)
 from .transformer_model import (  # noqa: F401
     TransformerModel, check_transformer_supported, initial_transformer_state)
+from .transformer_step import TransformerTrainer  # noqa: F401
 from .loop import evaluate, latest_path, train  # noqa: F401

@@ -125,6 +125,15 @@ def parse_args(arguments=None):
         '--log_interval', type=int, default=loop.LOG_INTERVAL,
         help='Steps between validations')
     parser.add_argument(
+        '--architecture', choices=('convolution', 'transformer'),
+        help="The model: 'convolution' (default), or 'transformer', which "
+             'trains through TransformerTrainer (downsample_location '
+             "'intermediate' or 'loss')")
+    parser.add_argument(
+        '--reference_dropout', action='store_true',
+        help="With the transformer: train with the reference's five "
+             "dropouts of 0.1 (precision 'f32' only)")
+    parser.add_argument(
         '--loss', choices=emphases_amd.config.LOSSES,
         help="The loss: 'bce' (default) or 'mse'")
     parser.add_argument(
@@ -177,7 +186,8 @@ def settings(arguments=None):
     path = arguments.pop('config')
     overrides, loop_arguments = ({}, {}) if path is None else \
         read_config(path)
-    for name in ('loss', 'downsample_method', 'downsample_location',
+    for name in ('architecture', 'loss', 'downsample_method',
+                 'downsample_location',
                  'upsample_method', 'activation', 'channels', 'layers',
                  'encoder_kernel_size', 'decoder_kernel_size', 'dropout'):
         value = arguments.pop(name)
@@ -195,6 +205,17 @@ def main(arguments=None):
     overrides, arguments = settings(arguments)
     if overrides:
         emphases_amd.configure(**overrides)
+    # (the Transformer is an opt-in of `train.train`: without it the keyword
+    # arguments are the ones they always were)
+    reference_dropout = arguments.pop('reference_dropout')
+    if emphases_amd.core.active_config().architecture == 'transformer':
+        arguments['trainer'] = emphases_amd.train.TransformerTrainer
+        if reference_dropout:
+            arguments['trainer_arguments'] = {'reference_dropout': True}
+    elif reference_dropout:
+        raise SystemExit(
+            'error: --reference_dropout goes with the transformer '
+            '(--architecture transformer, or ARCHITECTURE in --config)')
     dataset, directory = arguments.pop('dataset'), arguments.pop('directory')
     emphases_amd.train.train(dataset, directory, **arguments)
 

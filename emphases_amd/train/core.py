@@ -483,88 +483,47 @@ class Batch:
         self.targets = targets
 
 
-class _Step:
-    """What every step shares: the flat state, the batch layout, Adam, the
-    checkpoint, the workspace (`_buffers`) and every launch that more than
-    one step issues - a conv layer and a conv stack forward and backward, the
-    frame encoder, the reduce, and the word tail (output layer, loss, output
-    layer's backward).  A subclass names its `_check` and gives `_forward`
-    (whose buffers' 'logits' then hold the packed word logits) and
-    `_forward_backward` (which leaves the loss in `self.loss` and every
-    gradient in `self.gradients`)."""
+class _State:
+    """The state of a trainer and what does not depend on how its step is
+    computed: parameters, both Adam moments and the step count in flat device
+    buffers in `weights.parameter_shapes` order, the checkpoint
+    (`optimizer_state_dict`, `save`, and reading one back), and `prepare`, the
+    packed layout of a collated batch.  A subclass gives `metadata(plan)` and
+    `state_dict()`.  `_Step` (the fused steps) and `TransformerTrainer`
+    (`train/transformer_step.py`) are built on it."""
 
-    _check = staticmethod(check_supported)
-
-    def __init__(self, config=None, checkpoint=None, gpu=None, lr=1e-3,
-                 betas=(0.9, 0.999), eps=1e-8, seed=0, precision='f32'):
-        """precision: 'f32' (default) or 'bf16x3' (see the module docstring);
-        a choice of the configuration, never of the batch, and not part of
-        the checkpoint: a run saved at one resumes at the other.
-        seed: of the initialisation (without a checkpoint) and of the dropout
-        masks (always; `Config.dropout`).
-        checkpoint: None (the reference's initialisation under `seed`), a
-        state dict, or a file `weights.load` reads; a file written by `save`
-        also restores the Adam moments and the step count."""
-        self.config = config = config or api.active_config()
-        self._check(config)
-        self.precision = check_precision(precision)
+    def _settings(self, lr, betas, eps, seed):
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
         self.steps = 0
         self.seed = int(seed)
-        # (None and 0. launch nothing: torch.nn.Dropout(0.) is the identity)
-        self.dropout = float(config.dropout or 0.)
-        optimizer = None
-        if checkpoint is None:
-            state = initial_state(config, seed)
-        else:
-            if not isinstance(checkpoint, dict) and \
-                    not str(checkpoint).endswith('.npz'):
-                checkpoint = torch.load(
-                    os.fspath(checkpoint), map_location='cpu',
-                    weights_only=False)
-            if isinstance(checkpoint, dict) and 'model' in checkpoint:
-                optimizer = checkpoint.get('optimizer')
-                checkpoint = checkpoint['model']
-            state = weights_module.load(checkpoint, config)
-        self.offsets, self.count = parameter_offsets(config)
-        tables = gather_tables(config)
-        self.device = runtime.require_gpu(gpu)
-        self.lib = runtime.library()
-        with torch.cuda.device(self.device):
-            flat = np.concatenate([state[name].ravel() for name in self.offsets])
-            self.parameters = torch.from_numpy(flat).to(self.device)
-            self.gradients = torch.zeros_like(self.parameters)
-            self.exp_avg = torch.zeros_like(self.parameters)
-            self.exp_avg_sq = torch.zeros_like(self.parameters)
-            if optimizer is not None and optimizer.get('state'):
-                self._restore(optimizer)
-            self.take_index = torch.from_numpy(tables['index']).to(self.device)
-            self.packs = torch.zeros(
-                tables['index'].size, dtype=torch.float32, device=self.device)
-            self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-            self._forward_packs = tables['forward']
-            self._backward_packs = tables['backward']
-            self._workspace = {}
-            self._split_forward, self._split_backward = {}, {}
-            if self.precision == 'bf16x3':
-                tables = split_pack_tables(config)
-                self._split_forward = tables['forward']
-                self._split_backward = tables['backward']
-                self._split_bytes = int(
-                    self.lib.emph_conv_split_pack_size())
-                assert tables['index'].shape[1] * 4 == self._split_bytes
-                self.split_index = torch.from_numpy(
-                    tables['index']).to(self.device)
-                self.split_packs = torch.zeros(
-                    (tables['index'].shape[0], self._split_bytes),
-                    dtype=torch.uint8, device=self.device)
-                self._zero_bias = torch.zeros(
-                    SPLIT_CHANNELS, dtype=torch.float32, device=self.device)
-            self._repack()
 
-    ###########################################################################
-    # State
-    ###########################################################################
+    def _read(self, checkpoint, initial):
+        """(the parameters as numpy arrays by name, the optimizer state or
+        None) of `checkpoint`: None (`initial(config, seed)`), a state dict,
+        or a file `weights.load` reads; a file written by `save` carries the
+        optimizer state."""
+        if checkpoint is None:
+            return initial(self.config, self.seed), None
+        optimizer = None
+        if not isinstance(checkpoint, dict) and \
+                not str(checkpoint).endswith('.npz'):
+            checkpoint = torch.load(
+                os.fspath(checkpoint), map_location='cpu',
+                weights_only=False)
+        if isinstance(checkpoint, dict) and 'model' in checkpoint:
+            optimizer = checkpoint.get('optimizer')
+            checkpoint = checkpoint['model']
+        return weights_module.load(checkpoint, self.config), optimizer
+
+    def _allocate(self, state, optimizer):
+        """The flat device buffers of `state` (inside the device's context);
+        `optimizer`: the moments and the step count restored from it."""
+        flat = np.concatenate([state[name].ravel() for name in self.offsets])
+        self.parameters = torch.from_numpy(flat).to(self.device)
+        self.exp_avg = torch.zeros_like(self.parameters)
+        self.exp_avg_sq = torch.zeros_like(self.parameters)
+        if optimizer is not None and optimizer.get('state'):
+            self._restore(optimizer)
 
     def _view(self, buffer, name):
         first, shape = self.offsets[name]
@@ -584,15 +543,6 @@ class _Step:
         group = optimizer['param_groups'][0]
         self.lr, self.eps = float(group['lr']), float(group['eps'])
         self.betas = tuple(float(b) for b in group['betas'])
-
-    def state_dict(self):
-        """The parameters under the reference's names (`checkpoint_names`)
-        and shapes (CPU)."""
-        flat = self.parameters.cpu()
-        saved = checkpoint_names(self.config)
-        return collections.OrderedDict(
-            (saved[name], self._view(flat, name).clone())
-            for name in self.offsets)
 
     def optimizer_state_dict(self):
         """`torch.optim.Adam.state_dict()` of the reference's optimizer
@@ -654,6 +604,80 @@ class _Step:
                 plan.ld_words, 1, table[items:].data_ptr(), items,
                 runtime.stream()), 'emph_gather_columns')
         return Batch(plan, meta, packed, packed_targets)
+
+
+class _Step(_State):
+    """What every fused step shares on top of `_State`: the batch's integer
+    tables, Adam, the workspace (`_buffers`) and every launch that more than
+    one step issues - a conv layer and a conv stack forward and backward, the
+    frame encoder, the reduce, and the word tail (output layer, loss, output
+    layer's backward).  A subclass names its `_check` and gives `_forward`
+    (whose buffers' 'logits' then hold the packed word logits) and
+    `_forward_backward` (which leaves the loss in `self.loss` and every
+    gradient in `self.gradients`)."""
+
+    _check = staticmethod(check_supported)
+
+    def __init__(self, config=None, checkpoint=None, gpu=None, lr=1e-3,
+                 betas=(0.9, 0.999), eps=1e-8, seed=0, precision='f32'):
+        """precision: 'f32' (default) or 'bf16x3' (see the module docstring);
+        a choice of the configuration, never of the batch, and not part of
+        the checkpoint: a run saved at one resumes at the other.
+        seed: of the initialisation (without a checkpoint) and of the dropout
+        masks (always; `Config.dropout`).
+        checkpoint: None (the reference's initialisation under `seed`), a
+        state dict, or a file `weights.load` reads; a file written by `save`
+        also restores the Adam moments and the step count."""
+        self.config = config = config or api.active_config()
+        self._check(config)
+        self.precision = check_precision(precision)
+        self._settings(lr, betas, eps, seed)
+        # (None and 0. launch nothing: torch.nn.Dropout(0.) is the identity)
+        self.dropout = float(config.dropout or 0.)
+        state, optimizer = self._read(checkpoint, initial_state)
+        self.offsets, self.count = parameter_offsets(config)
+        tables = gather_tables(config)
+        self.device = runtime.require_gpu(gpu)
+        self.lib = runtime.library()
+        with torch.cuda.device(self.device):
+            self._allocate(state, optimizer)
+            self.gradients = torch.zeros_like(self.parameters)
+            self.take_index = torch.from_numpy(tables['index']).to(self.device)
+            self.packs = torch.zeros(
+                tables['index'].size, dtype=torch.float32, device=self.device)
+            self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self._forward_packs = tables['forward']
+            self._backward_packs = tables['backward']
+            self._workspace = {}
+            self._split_forward, self._split_backward = {}, {}
+            if self.precision == 'bf16x3':
+                tables = split_pack_tables(config)
+                self._split_forward = tables['forward']
+                self._split_backward = tables['backward']
+                self._split_bytes = int(
+                    self.lib.emph_conv_split_pack_size())
+                assert tables['index'].shape[1] * 4 == self._split_bytes
+                self.split_index = torch.from_numpy(
+                    tables['index']).to(self.device)
+                self.split_packs = torch.zeros(
+                    (tables['index'].shape[0], self._split_bytes),
+                    dtype=torch.uint8, device=self.device)
+                self._zero_bias = torch.zeros(
+                    SPLIT_CHANNELS, dtype=torch.float32, device=self.device)
+            self._repack()
+
+    ###########################################################################
+    # State
+    ###########################################################################
+
+    def state_dict(self):
+        """The parameters under the reference's names (`checkpoint_names`)
+        and shapes (CPU)."""
+        flat = self.parameters.cpu()
+        saved = checkpoint_names(self.config)
+        return collections.OrderedDict(
+            (saved[name], self._view(flat, name).clone())
+            for name in self.offsets)
 
     def _upload(self, tables):
         """Host tables [(int32 array, {name: (first element, size)})], every

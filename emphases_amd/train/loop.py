@@ -1,9 +1,11 @@
-"""The training loop of the convolution model (`emphases/train/core.py:13-307`):
-resume, train, validate, save - around `Trainer.step` (`EncoderTrainer.step`
-at downsample_location 'inference' and 'loss', `PieceTrainer.step` at 'input',
+"""The training loop (`emphases/train/core.py:13-307`): resume, train,
+validate, save - around `Trainer.step` (`EncoderTrainer.step` at
+downsample_location 'inference' and 'loss', `PieceTrainer.step` at 'input',
 `GridTrainer.step` for the rest of the hyperparameter grid at 'intermediate':
-`select_trainer`), fed by the resident
-loader of `emphases_amd.data`.
+`select_trainer`), fed by the resident loader of `emphases_amd.data`.  That
+dispatch covers the convolution model and refuses ARCHITECTURE =
+'transformer'; `train(..., trainer=TransformerTrainer)` runs the same loop
+around `TransformerTrainer.step`.
 
 Deviations from the reference, besides those of the step (`train/core.py`
 here: float32 or `precision='bf16x3'` in place of autocast, every utterance
@@ -27,6 +29,7 @@ final save after the loop.  A run resumes from the `*.pt` with the largest
 step number in `directory`, and restarts that file's epoch from its first
 batch, as the reference does.
 """
+import functools
 import json
 import os
 import re
@@ -101,15 +104,30 @@ def train(dataset, directory, gpu=None, *, partition_dir,
           cache_dir='data/cache', config=None, num_steps=NUM_STEPS,
           max_training_frames=MAX_TRAINING_FRAMES, log_interval=LOG_INTERVAL,
           log_steps=LOG_STEPS, save_after=SAVE_AFTER, seed=RANDOM_SEED,
-          precision='f32'):
-    """Train the convolution model on the 'train' partition of `dataset`,
-    validating on its 'valid' partition (`emphases.train`); checkpoints and
-    `scalars.jsonl` go to `directory`.  `precision`: 'f32' or 'bf16x3' of
-    `Trainer`, for the steps and for validation; the files do not record it.
+          precision='f32', trainer=None, trainer_arguments=None):
+    """Train the model on the 'train' partition of `dataset`, validating on
+    its 'valid' partition (`emphases.train`); checkpoints and `scalars.jsonl`
+    go to `directory`.  `precision`: 'f32' or 'bf16x3' of the step, for the
+    steps and for validation; the files do not record it.
+    `trainer`: None - the fused step `select_trainer` names for the
+    configuration (the convolution model; the Transformer is refused) - or a
+    class with `Trainer`'s interface and a `check(config, precision,
+    **trainer_arguments)` that makes its refusals before a GPU is needed:
+    `TransformerTrainer`.  `trainer_arguments`: further keyword arguments of
+    that class ({'reference_dropout': True}).
     Returns the final checkpoint's path."""
     from .. import data
     config = config or api.active_config()
-    core.step_class(config, precision)              # before any file is read
+    # (every refusal before any file is read or any directory is made)
+    if trainer is None:
+        if trainer_arguments:
+            raise ValueError('trainer_arguments go with a trainer= class')
+        core.step_class(config, precision)
+        build = core.select_trainer
+    else:
+        trainer_arguments = dict(trainer_arguments or {})
+        trainer.check(config, precision, **trainer_arguments)
+        build = functools.partial(trainer, **trainer_arguments)
     directory = os.fspath(directory)
     os.makedirs(directory, exist_ok=True)
 
@@ -128,12 +146,11 @@ def train(dataset, directory, gpu=None, *, partition_dir,
         score, best = float(state['score']), float(state['best'])
         # (the seed keys the dropout masks; the step count, which the
         # optimizer state restores, continues their stream)
-        trainer = core.select_trainer(
+        trainer = build(
             config, checkpoint=state, gpu=gpu, seed=seed,
             precision=precision)
     else:
-        trainer = core.select_trainer(
-            config, gpu=gpu, seed=seed, precision=precision)
+        trainer = build(config, gpu=gpu, seed=seed, precision=precision)
     train_loader = loader('train', trainer, max_training_frames)
     # (the reference's validation sampler is `Sampler(dataset)`: the default
     # frame budget whatever the training one is, `data/sampler.py:15,35`)

@@ -71,6 +71,16 @@ def check_transformer_supported(config):
         refuse('mel_feature', 'True (80..83 input features)')
 
 
+def check_reference_dropout(precision, reference_dropout):
+    """NotImplementedError for `reference_dropout=True` off precision 'f32':
+    the one refusal `TransformerModel` and `TransformerTrainer.check` make."""
+    if reference_dropout and precision != 'f32':
+        raise NotImplementedError(
+            'TransformerModel supports reference_dropout=True at '
+            f"precision 'f32' only, not precision={precision!r}: the "
+            'masked attention kernels are float32')
+
+
 _LAYER_ORDER = ('self_attn.in_proj_weight', 'self_attn.in_proj_bias',
                 'self_attn.out_proj.weight', 'self_attn.out_proj.bias',
                 'linear1.weight', 'linear1.bias', 'linear2.weight',
@@ -253,11 +263,7 @@ class TransformerModel(torch.nn.Module):
         check_transformer_supported(config)
         self.precision = check_precision(precision)
         self.reference_dropout = bool(reference_dropout)
-        if self.reference_dropout and self.precision != 'f32':
-            raise NotImplementedError(
-                'TransformerModel supports reference_dropout=True at '
-                f"precision 'f32' only, not precision={precision!r}: the "
-                'masked attention kernels are float32')
+        check_reference_dropout(self.precision, self.reference_dropout)
         self.seed, self.steps = int(seed), 0
         if checkpoint is None:
             state = initial_transformer_state(config, seed)

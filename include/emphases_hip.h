@@ -1325,6 +1325,27 @@ int emph_adam_step(float* parameter, const float* gradient, float* exp_avg,
                    float* exp_avg_sq, int64_t count, double beta1, double beta2,
                    float step_size, float correction2_sqrt, float eps, void* stream);
 
+/* emph_adam_step with the gradients where autograd left them: `tensors`
+ * gradient tensors, tensor t holding counts[t] floats at gradients[t] (device,
+ * contiguous, aligned to 4 bytes and to nothing more) for the elements
+ * offsets[t] .. offsets[t] + counts[t] - 1 of the flat buffers `parameters`,
+ * `exp_avg` and `exp_avg_sq`.  `gradients`, `offsets` and `counts` are HOST
+ * arrays: they travel in the kernel's arguments, EMPH_ADAM_TABLE tensors to a
+ * launch, so nothing is uploaded and nothing waits for the stream; 148
+ * tensors are two launches.  Every element gets emph_adam_step's arithmetic,
+ * evaluated by the same device function: the same bits as emph_adam_step run
+ * tensor by tensor.  A tensor of zero elements is skipped and takes no place
+ * in a table (its pointer is not looked at: null or anything else);
+ * tensors == 0 is EMPH_OK; a null gradient of a non-empty tensor, a
+ * negative count or offset is EMPH_EINVAL, a count of 2^30 or more
+ * EMPH_ERANGE - all found before the first launch, so a refusal updates
+ * nothing.  The ranges of two tensors must not overlap (not checked). */
+#define EMPH_ADAM_TABLE 96
+int emph_adam_step_gathered(float* parameters, const float* const* gradients,
+                            const int64_t* offsets, const int64_t* counts, int32_t tensors,
+                            float* exp_avg, float* exp_avg_sq, double beta1, double beta2,
+                            float step_size, float correction2_sqrt, float eps, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Backward of the operator seams (emphases_amd/ops.py under autograd)       */
 /* ------------------------------------------------------------------------ */

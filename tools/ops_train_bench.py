@@ -58,6 +58,21 @@ DIRECTORY` (with `--architecture transformer`, at either precision) adds
 `emph_attention_backward_split` - beside `emph_attention` and
 `emph_attention_backward` in the same run, with the MFMA flops they execute
 over the bf16 peak.
+
+`--trainer` (with `--architecture transformer`, at either precision):
+`trainer`, `emphases_amd.train.TransformerTrainer.step` on the prepared batch,
+against `ops`, the step of `TransformerModel` + `torch.optim.Adam` of this
+checkout at the same precision, and - `--parent DIRECTORY` - `ops_parent`,
+the same of that checkout.  `ops` and `ops_parent` each run in a child
+process (this file's `--serve`), lap for lap between the trainer's: two sets
+of 148 parameters stepping in one process outgrow the 256 entries of the ops'
+weight caches, and each would evict the other's on every step.  The record
+says whether the trainer's median lap is above the `ops` median by more than
+the laps' own spread.
+
+    python tools/ops_train_bench.py --architecture transformer --trainer \
+        [--precision bf16x3] [--parent <checkout, built>] \
+        [--out profiles/transformer_trainer_step.json]
 """
 import argparse
 import json
@@ -383,28 +398,96 @@ class Parent(train_bench.Parent):
     """The f32 Transformer step of another checkout of this package in a
     child process: this file's `--serve` on that checkout's package."""
 
-    def __init__(self, directory):
+    def __init__(self, directory, precision='f32'):
         import subprocess
         directory = os.path.abspath(directory)
         self.process = subprocess.Popen(
-            [sys.executable, os.path.abspath(__file__), '--serve'],
+            [sys.executable, os.path.abspath(__file__), '--serve',
+             '--precision', precision],
             cwd=directory, env=dict(os.environ, EMPHASES_BENCH_ROOT=directory),
             stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
 
 
-def serve():
+def serve(precision='f32'):
     """The child of `Parent`: 0 -> one step, its loss; n -> a timed lap.
-    (No `precision=`: the package may be older than the keyword.)"""
+    (No `precision=` at 'f32': the package may be older than the keyword.)"""
     torch.cuda.set_device(0)
     config = emphases_amd.Config(architecture='transformer', layers=6)
     state = train.initial_transformer_state(config, seed=0)
-    _, step = transformer_step(config, state)
+    _, step = transformer_step(
+        config, state, None if precision == 'f32' else precision)
     for line in sys.stdin:
         steps = int(line)
         if steps == 0:
             print(float(step()), flush=True)
         else:
             print(train_bench.timed(step, steps), flush=True)
+
+
+def trainer_main(arguments):
+    """`--trainer`: see the module docstring."""
+    torch.cuda.set_device(0)
+    items, frames, words = \
+        train_bench.ITEMS, train_bench.FRAMES, train_bench.WORDS
+    config = emphases_amd.Config(architecture='transformer', layers=6)
+    state = train.initial_transformer_state(config, seed=0)
+    trainer = train.TransformerTrainer(
+        config, checkpoint=state, gpu=0, precision=arguments.precision)
+    prepared = trainer.prepare(*train_bench.make_batch())
+    contenders = {'trainer': lambda: trainer.step(prepared),
+                  'ops': Parent(train_bench.ROOT, arguments.precision)}
+    if arguments.parent:
+        contenders['ops_parent'] = Parent(arguments.parent, arguments.precision)
+    first = {}
+    for name, function in contenders.items():
+        first[name] = float(function())
+        for _ in range(2):
+            function()
+    torch.cuda.synchronize()
+    steps = {}
+    for name, function in contenders.items():
+        probe = train_bench.run_lap(function, 2)
+        steps[name] = arguments.steps or max(
+            2, int(arguments.seconds * 1e3 / probe))
+    laps = {name: [] for name in contenders}
+    for _ in range(arguments.laps):
+        for name, function in contenders.items():
+            laps[name].append(train_bench.run_lap(function, steps[name]))
+    for function in contenders.values():
+        if isinstance(function, train_bench.Parent):
+            function.close()
+    record = {
+        'architecture': 'transformer', 'layers': config.layers,
+        'downsample_location': config.downsample_location,
+        'precision': arguments.precision,
+        'batch': {'utterances': items, 'frames': frames, 'words': words},
+        'device': torch.cuda.get_device_name(0),
+        'parameter_tensors': len(trainer.offsets),
+        'laps': arguments.laps, 'steps_per_lap': steps, 'first_loss': first,
+        'ms_per_step': {
+            name: {'median': float(np.median(values)),
+                   'min': float(np.min(values)), 'max': float(np.max(values))}
+            for name, values in laps.items()},
+        'ms_per_step_laps': laps}
+    median = {name: record['ms_per_step'][name]['median'] for name in laps}
+    spread = max(max(values) - min(values) for values in laps.values())
+    record['trainer_over_ops'] = median['trainer'] / median['ops']
+    record['laps_spread_ms'] = spread
+    # (no regression: the trainer's median lap is not above the model +
+    # torch.optim.Adam median by more than the laps' own spread)
+    record['trainer_within_the_spread_of_ops'] = bool(
+        median['trainer'] <= median['ops'] + spread)
+    if 'ops_parent' in laps:
+        record['trainer_over_ops_parent'] = \
+            median['trainer'] / median['ops_parent']
+        record['ops_over_ops_parent'] = median['ops'] / median['ops_parent']
+        record['trainer_within_the_spread_of_ops_parent'] = bool(
+            median['trainer'] <= median['ops_parent'] + spread)
+    print(json.dumps(record))
+    if arguments.out:
+        with open(arguments.out, 'w') as file:
+            json.dump(record, file, indent=1)
+            file.write('\n')
 
 
 def transformer_main(arguments):
@@ -541,6 +624,7 @@ def main():
     parser.add_argument('--precision', default='f32',
                         choices=('f32', 'bf16x3'))
     parser.add_argument('--parent', default=None)
+    parser.add_argument('--trainer', action='store_true')
     parser.add_argument('--serve', action='store_true')
     parser.add_argument('--laps', type=int, default=7)
     parser.add_argument('--seconds', type=float, default=1.0)
@@ -548,7 +632,13 @@ def main():
     parser.add_argument('--out', default=None)
     arguments = parser.parse_args()
     if arguments.serve:
-        return serve()
+        return serve(arguments.precision)
+    if arguments.trainer:
+        if arguments.architecture != 'transformer' or \
+                arguments.reference_dropout or arguments.kernels_out:
+            parser.error('--trainer goes with --architecture transformer, '
+                         'without --reference_dropout and --kernels-out')
+        return trainer_main(arguments)
     if arguments.precision != 'f32' and (
             arguments.architecture != 'transformer' or
             arguments.reference_dropout):
