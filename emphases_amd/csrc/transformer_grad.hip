@@ -121,12 +121,12 @@ __device__ __forceinline__ f32x4 scores_split(const float (&a)[KSTEPS], const fl
 // then D ([3][heads][ld] under DROP: the row maximum, D, 1 / sum).
 // DROP: the weights were dropped in the forward (emph_attention_dropout);
 // without it `mask` is unused and the code is that of the plain backward.
-template <int D, bool DROP>
+template <int D, bool DROP, bool KEYS>
 __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kernel(
     const float* __restrict__ qk, const float* __restrict__ v, const float* __restrict__ out,
     const float* __restrict__ dout, float* __restrict__ dqkv, float* __restrict__ stats,
     int64_t ld, int channels, int heads, const int32_t* __restrict__ tiles,
-    AttentionMask mask) {
+    const int32_t* __restrict__ key_counts, AttentionMask mask) {
     constexpr int QT = kGradTile / kGradWaves / 16;
     constexpr int KSTEPS = D / 4;
     constexpr int MT = (D + 15) / 16;
@@ -139,6 +139,18 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kern
     const int q0 = span.first + 16 * QT * wave;
     const int count = span.count;
     if (q0 >= count) return;                       // wave-uniform; no barrier below
+    // KEYS: only the segment's leading `keys` positions are keys, the rest is
+    // padding behind src_key_padding_mask (every position stays a query).  The
+    // loads below clamp to the last REAL key: a padded K or V row is never read.
+    const int keys = KEYS ? min(max(key_counts[span.segment], 1), count) : count;
+    // ONE real key in front of padding: the softmax is the constant 1 and its
+    // derivative zero.  dP (an MFMA chain) and D (dO . O, summed another way)
+    // are then two roundings of the same sum, and their difference, 4e-6 where
+    // the sums are of size 10, would stand in dQ and, added over the queries,
+    // in dK: dS is selected to 0 instead, as a softmax backward that takes D
+    // from P and dP gives it.  (Not without padding, n = k = 1: there the bits
+    // are those of the plain backward.)
+    const bool single = KEYS && keys == 1 && count > 1;
     const float scale = 1.f / sqrtf(static_cast<float>(D));
     const float scale2 = kLog2e * scale;
 
@@ -175,9 +187,9 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kern
         top[t] = -INFINITY;
         total[t] = 0.f;
     }
-    for (int key0 = 0; key0 < count; key0 += 16) {
+    for (int key0 = 0; key0 < keys; key0 += 16) {
         float ak[KSTEPS];
-        const int key = min(key0 + col, count - 1);
+        const int key = min(key0 + col, keys - 1);
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s)
             ak[s] = k_rows[static_cast<int64_t>(4 * s + kk) * ld + key];
@@ -199,7 +211,7 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kern
         for (int t = 0; t < QT; ++t) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (key0 + 4 * kk + r >= count) s4[t][r] = -INFINITY;
+                if (key0 + 4 * kk + r >= keys) s4[t][r] = -INFINITY;
             const float high =
                 fmaxf(fmaxf(fmaxf(s4[t][0], s4[t][1]), fmaxf(s4[t][2], s4[t][3])), top[t]);
             if (high > -INFINITY) {                // (a lane whose keys are all masked so far)
@@ -252,9 +264,9 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kern
     for (int t = 0; t < QT; ++t)
 #pragma unroll
         for (int m = 0; m < MT; ++m) dq[t][m] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int key0 = 0; key0 < count; key0 += 16) {
+    for (int key0 = 0; key0 < keys; key0 += 16) {
         float ak[KSTEPS], av[KSTEPS], akt[4][MT];
-        const int key = min(key0 + col, count - 1);
+        const int key = min(key0 + col, keys - 1);
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
             ak[s] = k_rows[static_cast<int64_t>(4 * s + kk) * ld + key];
@@ -262,7 +274,7 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kern
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int tkey = min(key0 + 4 * kk + r, count - 1);
+            const int tkey = min(key0 + 4 * kk + r, keys - 1);
 #pragma unroll
             for (int m = 0; m < MT; ++m)
                 akt[r][m] = k_rows[static_cast<int64_t>(min(16 * m + col, D - 1)) * ld + tkey];
@@ -293,7 +305,7 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kern
                                                                   0, 0);
                 }
         }
-        // a key past the segment: probability 0 (selected; the clamped loads
+        // a key past the last one: probability 0 (selected; the clamped loads
         // above only feed such rows)
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
@@ -310,9 +322,9 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kern
             for (int r = 0; r < 4; ++r) {
                 float exponent = s4[t][r] - lse[t];
                 if constexpr (DROP) exponent += low4[t][r];
-                float p = key0 + 4 * kk + r < count ? __builtin_amdgcn_exp2f(exponent) : 0.f;
+                float p = key0 + 4 * kk + r < keys ? __builtin_amdgcn_exp2f(exponent) : 0.f;
                 if constexpr (DROP) p *= inverse[t];
-                s4[t][r] = p * (dp4[t][r] - delta[t]);
+                s4[t][r] = single ? 0.f : p * (dp4[t][r] - delta[t]);
             }
         }
 #pragma unroll
@@ -340,12 +352,15 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_query_kern
 }
 
 // grid = (n_tiles, heads); block = 128: wave w owns keys [32 w, 32 w + 32) of
-// the tile and walks the segment's queries 16 at a time.
-template <int D, bool DROP>
+// the tile and walks the segment's queries 16 at a time.  KEYS: a block of 16
+// keys at or past the segment's last real key does no MFMA work and a padded
+// key's dK and dV columns are stored as zeros.
+template <int D, bool DROP, bool KEYS>
 __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_key_kernel(
     const float* __restrict__ qk, const float* __restrict__ v, const float* __restrict__ dout,
     float* __restrict__ dqkv, const float* __restrict__ stats, int64_t ld, int channels,
-    int heads, const int32_t* __restrict__ tiles, AttentionMask mask) {
+    int heads, const int32_t* __restrict__ tiles, const int32_t* __restrict__ key_counts,
+    AttentionMask mask) {
     constexpr int KT = kGradTile / kGradWaves / 16;
     constexpr int KSTEPS = D / 4;
     constexpr int MT = (D + 15) / 16;
@@ -358,6 +373,10 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_key_kernel
     const int k0 = span.first + 16 * KT * wave;
     const int count = span.count;
     if (k0 >= count) return;                       // wave-uniform; no barrier below
+    const int keys = KEYS ? min(max(key_counts[span.segment], 1), count) : count;
+    const bool real = !KEYS || k0 < keys;          // wave-uniform: any real key here
+    // (one real key in front of padding: dS = 0, see the query pass)
+    const bool single = KEYS && keys == 1 && count > 1;
     const float scale = 1.f / sqrtf(static_cast<float>(D));
     const float scale2 = kLog2e * scale;
 
@@ -370,11 +389,12 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_key_kernel
     const float* delta_row = stats + static_cast<int64_t>(heads + head) * ld + span.offset;
 
     // B operands of the key tile: K^T (scaled into log2 units) and V^T.  A key
-    // past the segment is a clamped copy: its column is never stored.
+    // past the last one is a clamped copy: its column is never stored (KEYS:
+    // stored as zeros).
     float bk[KT][KSTEPS], bv[KT][KSTEPS];
 #pragma unroll
     for (int u = 0; u < KT; ++u) {
-        const int key = min(k0 + 16 * u + col, count - 1);
+        const int key = min(k0 + 16 * u + col, keys - 1);
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
             bk[u][s] = k_rows[static_cast<int64_t>(4 * s + kk) * ld + key] * scale2;
@@ -390,7 +410,7 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_key_kernel
             dv[u][m] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
 
-    for (int q0 = 0; q0 < count; q0 += 16) {
+    for (int q0 = 0; q0 < (real ? count : 0); q0 += 16) {
         float aq[KSTEPS], ado[KSTEPS], aqt[4][MT], adot[4][MT], lse[4], delta[4], inverse[4];
         const int query = min(q0 + col, count - 1);
 #pragma unroll
@@ -416,6 +436,7 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_key_kernel
         }
 #pragma unroll
         for (int u = 0; u < KT; ++u) {
+            if (KEYS && k0 + 16 * u >= keys) continue;     // wave-uniform: padding only
             f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
             f32x4 dp4 = f32x4{0.f, 0.f, 0.f, 0.f};
             f32x4 low4;
@@ -460,7 +481,7 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_key_kernel
                     dp4[r] = p * ((kept ? dp4[r] * mask.scale : 0.f) - delta[r]);
                 } else {
                     s4[r] = p;
-                    dp4[r] = p * (dp4[r] - delta[r]);
+                    dp4[r] = single ? 0.f : p * (dp4[r] - delta[r]);
                 }
             }
 #pragma unroll
@@ -480,14 +501,16 @@ __global__ __launch_bounds__(64 * kGradWaves) void attention_backward_key_kernel
     for (int u = 0; u < KT; ++u) {
         const int key = k0 + 16 * u + col;
         if (key >= count) continue;
+        const bool padded = key >= keys;           // (never without KEYS)
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int d = 16 * m + 4 * kk + r;
                 if (d < D) {
-                    dk_rows[static_cast<int64_t>(d) * ld + key] = dk[u][m][r] * scale;
-                    dv_rows[static_cast<int64_t>(d) * ld + key] = dv[u][m][r];
+                    dk_rows[static_cast<int64_t>(d) * ld + key] =
+                        padded ? 0.f : dk[u][m][r] * scale;
+                    dv_rows[static_cast<int64_t>(d) * ld + key] = padded ? 0.f : dv[u][m][r];
                 }
             }
     }
@@ -782,30 +805,68 @@ int64_t emph_attention_backward_workspace(int64_t ld, int32_t heads) {
     return 2 * static_cast<int64_t>(heads) * ld;
 }
 
+// The body of emph_attention_backward (`key_counts` NULL: every position a
+// key) and of emph_attention_backward_keys, under the entry's own `name`.
+static int attention_backward_launch(const char* name, const float* qk, const float* v,
+                                     const float* out, const float* dout, float* dqkv,
+                                     int64_t ld, int32_t channels, int32_t heads,
+                                     const int32_t* tiles, int32_t n_tiles, int32_t tile_n,
+                                     const int32_t* key_counts, float* workspace,
+                                     void* stream) {
+    EMPH_REQUIRE(heads > 0 && channels > 0 && channels % heads == 0 && channels == 80 &&
+                     heads == 2,
+                 EMPH_ERANGE,
+                 "%s: channels %d, heads %d (only 80 channels in 2 heads of 40)", name,
+                 channels, heads);
+    EMPH_REQUIRE(tile_n == kGradTile, EMPH_EINVAL, "%s: tile_n %d (the 64-wide tile table)",
+                 name, tile_n);
+    EMPH_REQUIRE(n_tiles >= 0 && ld > 0, EMPH_EINVAL, "%s: bad shape", name);
+    if (n_tiles == 0) return EMPH_OK;
+    EMPH_REQUIRE(qk && v && out && dout && dqkv && tiles && workspace, EMPH_EINVAL,
+                 "%s: null pointer", name);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    dim3 grid(n_tiles, heads);
+    if (key_counts != nullptr)
+        EMPH_LAUNCH((attention_backward_query_kernel<40, false, true>), grid,
+                    dim3(64 * kGradWaves), 0, s, qk, v, out, dout, dqkv, workspace, ld,
+                    channels, heads, tiles, key_counts, AttentionMask{});
+    else
+        EMPH_LAUNCH((attention_backward_query_kernel<40, false, false>), grid,
+                    dim3(64 * kGradWaves), 0, s, qk, v, out, dout, dqkv, workspace, ld,
+                    channels, heads, tiles, key_counts, AttentionMask{});
+    int status = check_launch(key_counts != nullptr ? "emph_attention_backward_keys (queries)"
+                                                    : "emph_attention_backward (queries)");
+    if (status != EMPH_OK) return status;
+    if (key_counts != nullptr)
+        EMPH_LAUNCH((attention_backward_key_kernel<40, false, true>), grid,
+                    dim3(64 * kGradWaves), 0, s, qk, v, dout, dqkv, workspace, ld, channels,
+                    heads, tiles, key_counts, AttentionMask{});
+    else
+        EMPH_LAUNCH((attention_backward_key_kernel<40, false, false>), grid,
+                    dim3(64 * kGradWaves), 0, s, qk, v, dout, dqkv, workspace, ld, channels,
+                    heads, tiles, key_counts, AttentionMask{});
+    return check_launch(key_counts != nullptr ? "emph_attention_backward_keys (keys)"
+                                              : "emph_attention_backward (keys)");
+}
+
 int emph_attention_backward(const float* qk, const float* v, const float* out,
                             const float* dout, float* dqkv, int64_t ld, int32_t channels,
                             int32_t heads, const int32_t* tiles, int32_t n_tiles,
                             int32_t tile_n, float* workspace, void* stream) {
-    EMPH_REQUIRE(heads > 0 && channels > 0 && channels % heads == 0 && channels == 80 &&
-                     heads == 2,
-                 EMPH_ERANGE,
-                 "emph_attention_backward: channels %d, heads %d (only 80 channels in 2 heads "
-                 "of 40)", channels, heads);
-    EMPH_REQUIRE(tile_n == kGradTile, EMPH_EINVAL,
-                 "emph_attention_backward: tile_n %d (the 64-wide tile table)", tile_n);
-    EMPH_REQUIRE(n_tiles >= 0 && ld > 0, EMPH_EINVAL, "emph_attention_backward: bad shape");
-    if (n_tiles == 0) return EMPH_OK;
-    EMPH_REQUIRE(qk && v && out && dout && dqkv && tiles && workspace, EMPH_EINVAL,
-                 "emph_attention_backward: null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    dim3 grid(n_tiles, heads);
-    EMPH_LAUNCH((attention_backward_query_kernel<40, false>), grid, dim3(64 * kGradWaves), 0, s,
-                qk, v, out, dout, dqkv, workspace, ld, channels, heads, tiles, AttentionMask{});
-    int status = check_launch("emph_attention_backward (queries)");
-    if (status != EMPH_OK) return status;
-    EMPH_LAUNCH((attention_backward_key_kernel<40, false>), grid, dim3(64 * kGradWaves), 0, s,
-                qk, v, dout, dqkv, workspace, ld, channels, heads, tiles, AttentionMask{});
-    return check_launch("emph_attention_backward (keys)");
+    return attention_backward_launch("emph_attention_backward", qk, v, out, dout, dqkv, ld,
+                                     channels, heads, tiles, n_tiles, tile_n, nullptr,
+                                     workspace, stream);
+}
+
+int emph_attention_backward_keys(const float* qk, const float* v, const float* out,
+                                 const float* dout, float* dqkv, int64_t ld, int32_t channels,
+                                 int32_t heads, const int32_t* tiles, int32_t n_tiles,
+                                 int32_t tile_n, const int32_t* key_counts, float* workspace,
+                                 void* stream) {
+    return attention_backward_launch(
+        key_counts != nullptr ? "emph_attention_backward_keys" : "emph_attention_backward", qk,
+        v, out, dout, dqkv, ld, channels, heads, tiles, n_tiles, tile_n, key_counts, workspace,
+        stream);
 }
 
 // (word 1 of the counter, head ld + column, stays inside 32 bits)
@@ -869,12 +930,14 @@ int emph_attention_dropout_backward(const float* qk, const float* v, const float
     hipStream_t s = static_cast<hipStream_t>(stream);
     dim3 grid(n_tiles, heads);
     const AttentionMask mask = attention_mask(p, seed, stream_id, step);
-    EMPH_LAUNCH((attention_backward_query_kernel<40, true>), grid, dim3(64 * kGradWaves), 0, s,
-                qk, v, out, dout, dqkv, workspace, ld, channels, heads, tiles, mask);
+    EMPH_LAUNCH((attention_backward_query_kernel<40, true, false>), grid,
+                dim3(64 * kGradWaves), 0, s, qk, v, out, dout, dqkv, workspace, ld, channels,
+                heads, tiles, static_cast<const int32_t*>(nullptr), mask);
     int status = check_launch("emph_attention_dropout_backward (queries)");
     if (status != EMPH_OK) return status;
-    EMPH_LAUNCH((attention_backward_key_kernel<40, true>), grid, dim3(64 * kGradWaves), 0, s,
-                qk, v, dout, dqkv, workspace, ld, channels, heads, tiles, mask);
+    EMPH_LAUNCH((attention_backward_key_kernel<40, true, false>), grid, dim3(64 * kGradWaves),
+                0, s, qk, v, dout, dqkv, workspace, ld, channels, heads, tiles,
+                static_cast<const int32_t*>(nullptr), mask);
     return check_launch("emph_attention_dropout_backward (keys)");
 }
 

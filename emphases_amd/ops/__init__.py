@@ -15,11 +15,14 @@ prefix sums, so that a caller of the reference's ATen ops
     torch.ops.emphases_amd.encoder_layer_split(x, <the same twelve>, cu_T, heads,
                                          precision)                    the plain layer, its
                                          attention core on the bf16 matrix pipe
+    torch.ops.emphases_amd.encoder_layer_padded(x, <the same twelve>, cu_T, key_counts,
+                                         heads)                        transformer.py:26-29:
+                                         the plain layer behind src_key_padding_mask
     torch.ops.emphases_amd.dropout(x, p, seed, stream, step)           transformer.py:51-52
     torch.ops.emphases_amd.prominence_forward(audio_packed, cu_samples, bounds, cu_words)
                                                                        core.py:295-342
 
-The package: this module holds the eight ops, their fakes and their autograd
+The package: this module holds the nine ops, their fakes and their autograd
 registrations; `layout` the prefix sums, the plans, `_Layout` and the plan LRU;
 `packs` the launch helper `_call`, `_ByStorage` and everything kept per weight;
 `layer` the launchers an op shares with its backward and `_LayerRun`.
@@ -45,7 +48,9 @@ under the reference's four dropouts as specified masks - one body serves
 both, `dropout=None` being the plain layer; `encoder_layer_split` is the
 plain layer at `precision='bf16x3'`, the third caller of that body: the
 attention core of every segment of at least 128 positions on the bf16 matrix
-pipe, forward and backward - and `dropout` the mask alone) and `logmel` (gradient of a float `audio_packed`: the
+pipe, forward and backward; `encoder_layer_padded` is the plain layer whose
+segments end in zero padding that is no key, the fourth caller, walked back
+through `emph_attention_backward_keys` - and `dropout` the mask alone) and `logmel` (gradient of a float `audio_packed`: the
 waveform end of the chain, so d(prominence)/d(audio) exists on the seams; no
 `register_fake` - its shape depends on the values of `cu_samples`);
 `prominence_forward` alone stays non-differentiable.  The backward runs on
@@ -103,8 +108,8 @@ from .packs import (  # noqa: F401
     _layer_engine, _weight_changes, mark_trained, pack_index_tables)
 
 __all__ = ['logmel', 'conv1d_same_act', 'segment_reduce', 'encoder_layer',
-           'encoder_layer_dropout', 'encoder_layer_split', 'dropout',
-           'prominence_forward']
+           'encoder_layer_dropout', 'encoder_layer_split',
+           'encoder_layer_padded', 'dropout', 'prominence_forward']
 
 
 @torch.library.custom_op('emphases_amd::logmel', mutates_args=())
@@ -451,10 +456,33 @@ def _split_pieces(precision):
     return SPLIT_PIECES[precision]
 
 
-def _layer_forward(x, tensors, cu_T, heads, dropout=None, precision=None):
+def _key_counts(key_counts, layout):
+    """The device table of `key_counts` (int host tensor [N], the real
+    positions of every segment of `layout`), checked on the host when the
+    layout does not hold these values already (the backward asks again)."""
+    if key_counts.is_cuda or key_counts.is_floating_point():
+        raise TypeError('key_counts is an integer host tensor, like cu_T')
+
+    def check(counts):
+        frames = np.asarray(layout.plan.frames, dtype=np.int64)
+        if counts.shape != frames.shape:
+            raise ValueError(
+                f'key_counts has shape {tuple(counts.shape)}: one count for '
+                f'each of the {frames.size} segments of cu_T')
+        if np.any(counts < 1) or np.any(counts > frames):
+            raise ValueError(
+                'key_counts[i] must lie in 1 .. T_i (the real positions of '
+                'segment i, at least one)')
+    return layout.key_counts(
+        key_counts.detach().to(torch.int64).numpy(), check)
+
+
+def _layer_forward(x, tensors, cu_T, heads, dropout=None, precision=None,
+                   key_counts=None):
     """The body of `encoder_layer` (`dropout` None), of
-    `encoder_layer_dropout` (`dropout` = (p, seed, stream_base, step)) and of
-    `encoder_layer_split` (`precision`)."""
+    `encoder_layer_dropout` (`dropout` = (p, seed, stream_base, step)), of
+    `encoder_layer_split` (`precision`) and of `encoder_layer_padded`
+    (`key_counts`)."""
     pieces = 0
     if precision is not None:
         pieces = _split_pieces(precision)
@@ -463,15 +491,21 @@ def _layer_forward(x, tensors, cu_T, heads, dropout=None, precision=None):
         _check_layer_shape('encoder_layer_dropout', int(x.shape[0]), int(heads))
         dropout = _mask_arguments(*dropout)
     index, tensors, layout = _layer_inputs(x, tensors, cu_T)
+    if key_counts is not None:
+        _check_layer_shape('encoder_layer_padded', int(x.shape[0]), int(heads))
+        if x.dtype != torch.float32:
+            raise TypeError(f'encoder_layer_padded takes float32, not {x.dtype}')
+        key_counts = _key_counts(key_counts, layout)
     # (the plain layer of a parameter set that never changed is the fused
     # engine's, which alone takes a `cu_T` that covers fewer columns)
-    unfused = dropout is not None or pieces or \
+    unfused = dropout is not None or pieces or key_counts is not None or \
         any([_weight_changes(tensor) for tensor in tensors])
     if unfused and layout.frame_columns.numel() != x.shape[1]:
         raise ValueError('cu_T does not cover the columns of x')
     if unfused:
         with torch.cuda.device(index):
-            run = _LayerRun(x, tensors, heads, layout, index, dropout, pieces)
+            run = _LayerRun(x, tensors, heads, layout, index, dropout, pieces,
+                            key_counts)
             return run.normed2.index_select(1, layout.frame_columns)
     engine = _layer_engine(tensors, index, int(x.shape[0]), int(heads))
     plan = layout.plan
@@ -492,11 +526,15 @@ def _layer_fake(x, *rest):
 def _layer_setup(kind):
     """`setup_context` of the layer op `kind`: what follows `heads` in its
     inputs is nothing ('encoder_layer'), the four mask arguments
-    ('encoder_layer_dropout') or `precision` ('encoder_layer_split')."""
+    ('encoder_layer_dropout') or `precision` ('encoder_layer_split');
+    'encoder_layer_padded' has `key_counts` IN FRONT of `heads`."""
     def setup(ctx, inputs, output):
         ctx.kind = kind
+        ctx.key_counts = None
         ctx.heads = inputs[14]
         ctx.extra = len(inputs) - 15
+        if kind == 'encoder_layer_padded':
+            ctx.key_counts, ctx.heads = inputs[14], inputs[15]
         ctx.dropout = tuple(inputs[15:19]) \
             if kind == 'encoder_layer_dropout' else None
         ctx.precision = inputs[15] if kind == 'encoder_layer_split' else None
@@ -523,7 +561,9 @@ def _layer_backward(ctx, grad):
         run = _LayerRun(
             x.detach(), tensors, ctx.heads, layout, index,
             None if plain else _mask_arguments(*ctx.dropout),
-            0 if ctx.precision is None else _split_pieces(ctx.precision))
+            0 if ctx.precision is None else _split_pieces(ctx.precision),
+            None if ctx.key_counts is None
+            else _key_counts(ctx.key_counts, layout))
         grads = run.backward(grad, need)
         if grads[0] is not None:
             grads[0] = grads[0].index_select(1, layout.frame_columns)
@@ -637,9 +677,41 @@ def encoder_layer_split(
         cu_T, heads, precision=precision)
 
 
+@torch.library.custom_op('emphases_amd::encoder_layer_padded', mutates_args=())
+def encoder_layer_padded(
+        x: torch.Tensor, in_proj_weight: torch.Tensor,
+        in_proj_bias: torch.Tensor, out_proj_weight: torch.Tensor,
+        out_proj_bias: torch.Tensor, norm1_weight: torch.Tensor,
+        norm1_bias: torch.Tensor, linear1_weight: torch.Tensor,
+        linear1_bias: torch.Tensor, linear2_weight: torch.Tensor,
+        linear2_bias: torch.Tensor, norm2_weight: torch.Tensor,
+        norm2_bias: torch.Tensor, cu_T: torch.Tensor,
+        key_counts: torch.Tensor, heads: int) -> torch.Tensor:
+    """`encoder_layer` behind `src_key_padding_mask` (`transformer.py:26-29`):
+    segment i of `cu_T` holds `key_counts[i]` real positions followed by zero
+    padding (a word piece padded to the longest word, `batch.Pieces`).  Every
+    position is a query and gets an output, the padded ones too; only the
+    leading `key_counts[i]` are keys.  `key_counts`: integer host tensor [N]
+    like `cu_T`, checked on the host, 1 <= key_counts[i] <= T_i (ValueError).
+
+    Always the unfused sequence of `_LayerRun`, `emph_attention` taking the
+    table; dropout is the identity.  Backward (once): recomputed and walked
+    back through `emph_attention_backward_keys`, which writes dK and dV of a
+    padded position as zeros, so in_proj's gradients take nothing from the
+    padding's keys and values.  With `key_counts == T` everywhere the bits of
+    `encoder_layer` on updated parameters.  float32 x, 80 channels in 2 heads
+    only (TypeError, NotImplementedError)."""
+    return _layer_forward(
+        x, (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias,
+            norm1_weight, norm1_bias, linear1_weight, linear1_bias,
+            linear2_weight, linear2_bias, norm2_weight, norm2_bias),
+        cu_T, heads, key_counts=key_counts)
+
+
 for _kind, _op in (('encoder_layer', encoder_layer),
                    ('encoder_layer_dropout', encoder_layer_dropout),
-                   ('encoder_layer_split', encoder_layer_split)):
+                   ('encoder_layer_split', encoder_layer_split),
+                   ('encoder_layer_padded', encoder_layer_padded)):
     _op.register_fake(_layer_fake)
     _op.register_autograd(
         _layer_backward, setup_context=_layer_setup(_kind))

@@ -61,15 +61,26 @@ class _LayerRun:
     matrix pipe for the segments of at least `engine.GROUPED_FROM` positions
     (`emph_split_kv` + `emph_attention_split`, `emph_attention_backward_split`);
     shorter ones keep the fp32 kernels through a tile table of their own.  By
-    segment length alone: a segment's result does not depend on the batch."""
+    segment length alone: a segment's result does not depend on the batch.
+
+    `key_counts` (int32 device table, one per segment: `_Layout.key_counts`):
+    only a segment's leading `key_counts[i]` positions are keys, the rest is
+    zero padding behind `src_key_padding_mask`; `emph_attention` takes the
+    table and the way back is `emph_attention_backward_keys`.  Neither with
+    `dropout` nor with `pieces`."""
 
     def __init__(self, x, tensors, heads, layout, index, dropout=None,
-                 pieces=0):
+                 pieces=0, key_counts=None):
         (self.in_w, self.in_b, self.out_w, self.out_b, self.norm1_w,
          self.norm1_b, self.ff1_w, self.ff1_b, self.ff2_w, self.ff2_b,
          self.norm2_w, self.norm2_b) = tensors
         self.layout, self.index, self.heads = layout, index, int(heads)
         self.dropout, self.pieces = dropout, int(pieces)
+        self.key_counts = key_counts
+        if key_counts is not None and (dropout is not None or self.pieces):
+            raise NotImplementedError(
+                'key_counts with dropout or with pieces: the masked and the '
+                'bf16 attention kernels take no key-padding mask')
         self.ld = ld = layout.plan.ld_frames
         self.channels = channels = int(x.shape[0])
         self.device = x.device
@@ -130,7 +141,7 @@ class _LayerRun:
     def attention(self):
         """`attended` of `qk` and `v`; under `dropout` the masked kernel with
         its four mask arguments."""
-        name, tile, mask = 'emph_attention', DIRECT_TILE, (None,)
+        name, tile, mask = 'emph_attention', DIRECT_TILE, (self.key_counts,)
         if self.dropout is not None:
             name, tile, mask = 'emph_attention_dropout', GRAD_TILE, self.dropout
         tiles, n_tiles = self.tiles, self.n_tiles
@@ -181,13 +192,16 @@ class _LayerRun:
 
     def attention_backward(self, dattended):
         """dQ | dK | dV [3 C, ld] of `dattended`; under `dropout` the masked
-        kernel with its four mask arguments."""
+        kernel with its four mask arguments, under `key_counts` the padded
+        one with the table in front of the workspace."""
         name, mask = 'emph_attention_backward', ()
         if self.dropout is not None:
             name, mask = 'emph_attention_dropout_backward', self.dropout
         dqkv = self.zeros(3 * self.channels)
         library = runtime.library()
         sizes = [getattr(library, name + '_workspace')]
+        if self.key_counts is not None:
+            name = 'emph_attention_backward_keys'
         if self.pieces:
             # (one buffer serves both launches: they walk other segments)
             sizes.append(library.emph_attention_backward_split_workspace)
@@ -199,9 +213,10 @@ class _LayerRun:
             tiles, n_tiles = self.layout.tiles(GRAD_TILE, engine_module.SHORT)
             self.attention_backward_split(dattended, dqkv, workspace)
         if n_tiles or not self.pieces:
+            table = () if self.key_counts is None else (self.key_counts,)
             _call(name, self.qk, self.v, self.attended, dattended, dqkv,
                   self.ld, self.channels, self.heads, tiles, n_tiles,
-                  GRAD_TILE, workspace, *mask)
+                  GRAD_TILE, *table, workspace, *mask)
         return dqkv
 
     def attention_backward_split(self, dattended, dqkv, workspace):

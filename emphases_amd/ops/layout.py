@@ -109,6 +109,23 @@ class _Layout:
         tiles, size = self.meta[key]
         return tiles, size // runtime.TILE_FIELDS
 
+    def key_counts(self, counts, check=None):
+        """The int32 device table of `counts` (int64 host array, one per
+        segment) that `emph_attention` indexes by `Tile.segment`.  The layout
+        keeps its LAST table alone (a layer's forward, the layers behind it
+        and their backwards ask for the same one; a training loop brings a
+        new one with nearly every batch): `check(counts)` runs and the table
+        is uploaded only when the values differ from the kept ones."""
+        key = counts.tobytes()
+        kept = self.meta.get('key_counts')
+        if kept is None or kept[1] != key:
+            if check is not None:
+                check(counts)
+            host = np.ascontiguousarray(counts, dtype=np.int32)
+            kept = (torch.from_numpy(host).to(self.buffer.device), key)
+            self.meta['key_counts'] = kept
+        return kept[0]
+
     scatter = staticmethod(packed.scatter)
 
 

@@ -269,6 +269,9 @@ SIGNATURES = {
     'emph_attention_backward': (_c.c_int, [
         _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i32, _i32, _ptr, _i32, _i32, _ptr,
         _ptr]),
+    'emph_attention_backward_keys': (_c.c_int, [
+        _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i32, _i32, _ptr, _i32, _i32, _ptr,
+        _ptr, _ptr]),
     'emph_attention_backward_split_workspace': (_i64, [_i64, _i32]),
     'emph_attention_backward_split_bytes': (_i64, [_i64, _i32, _i32, _i32]),
     'emph_attention_backward_split': (_c.c_int, [

@@ -8,7 +8,11 @@ differentiable operator seams for the configurations the fused steps refuse.
 `TransformerTrainer` the step around it with the fused steps' interface: the
 fused steps and their dispatch (`step_class` ... `make_trainer`) refuse the
 architecture, and so does `train` unless it is given
-`trainer=TransformerTrainer`.
+`trainer=TransformerTrainer`.  `TransformerLocationsModel` and
+`TransformerLocationsTrainer` are the same pair at all four locations
+('input' through `ops.encoder_layer_padded`, 'inference' with the frame-rate
+head and upsampled targets), a second opt-in: the first pair keeps refusing
+those two.
 
 The fused steps, one class per `downsample_location` and one behind them:
 `Trainer` ('intermediate'), `EncoderTrainer` ('inference' and 'loss', no word
@@ -29,6 +33,8 @@ from . import dropout  # noqa: F401
 from .model import (  # noqa: F401
     TorchModel, check_model_supported, initial_model_state, loss_fn)
 from .transformer_model import (  # noqa: F401
-    TransformerModel, check_transformer_supported, initial_transformer_state)
-from .transformer_step import TransformerTrainer  # noqa: F401
+    TransformerLocationsModel, TransformerModel, check_locations_supported,
+    check_transformer_supported, initial_transformer_state)
+from .transformer_step import (  # noqa: F401
+    TransformerLocationsTrainer, TransformerTrainer)
 from .loop import evaluate, latest_path, train  # noqa: F401

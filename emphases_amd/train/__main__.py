@@ -128,7 +128,8 @@ def parse_args(arguments=None):
         '--architecture', choices=('convolution', 'transformer'),
         help="The model: 'convolution' (default), or 'transformer', which "
              'trains through TransformerTrainer (downsample_location '
-             "'intermediate' or 'loss')")
+             "'intermediate' or 'loss') or TransformerLocationsTrainer "
+             "('input' or 'inference')")
     parser.add_argument(
         '--reference_dropout', action='store_true',
         help="With the transformer: train with the reference's five "
@@ -142,10 +143,12 @@ def parse_args(arguments=None):
              "'center'")
     parser.add_argument(
         '--downsample_location',
-        choices=('intermediate', 'inference', 'loss'),
+        choices=('input', 'intermediate', 'inference', 'loss'),
         help="Where the frames become words: 'intermediate' (default, with "
              "a word decoder), 'inference' (frame-rate loss against "
-             "upsampled targets) or 'loss' (word-rate loss, no decoder)")
+             "upsampled targets), 'loss' (word-rate loss, no decoder) or, "
+             "with the transformer only, 'input' (every word a padded piece "
+             'of its own)')
     parser.add_argument(
         '--upsample_method', choices=emphases_amd.config.UPSAMPLE_METHODS,
         help="The interpolation of the targets at --downsample_location "
@@ -175,7 +178,13 @@ def parse_args(arguments=None):
         '--precision', choices=emphases_amd.train.PRECISIONS, default='f32',
         help="'f32' (default), or 'bf16x3': the frame-rate convolutions of "
              'the step on the bf16 matrix pipe, two pieces per operand')
-    return parser.parse_args(arguments)
+    parsed = parser.parse_args(arguments)
+    if parsed.downsample_location == 'input' and parsed.config is None and \
+            parsed.architecture != 'transformer':
+        parser.error("--downsample_location input goes with --architecture "
+                     "transformer (the convolution model takes 'input' from "
+                     'a --config file)')
+    return parsed
 
 
 def settings(arguments=None):
@@ -208,8 +217,13 @@ def main(arguments=None):
     # (the Transformer is an opt-in of `train.train`: without it the keyword
     # arguments are the ones they always were)
     reference_dropout = arguments.pop('reference_dropout')
-    if emphases_amd.core.active_config().architecture == 'transformer':
-        arguments['trainer'] = emphases_amd.train.TransformerTrainer
+    active = emphases_amd.core.active_config()
+    if active.architecture == 'transformer':
+        # ('intermediate' and 'loss' keep the trainer they always had)
+        located = active.downsample_location in ('input', 'inference')
+        arguments['trainer'] = \
+            emphases_amd.train.TransformerLocationsTrainer if located \
+            else emphases_amd.train.TransformerTrainer
         if reference_dropout:
             arguments['trainer_arguments'] = {'reference_dropout': True}
     elif reference_dropout:

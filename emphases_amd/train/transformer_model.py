@@ -43,9 +43,14 @@ from . import dropout as spec
 CHANNELS, HEADS = 80, 2     # the backward of encoder_layer
 
 
-def check_transformer_supported(config):
+LOCATIONS = ('intermediate', 'loss')                    # TransformerModel
+ALL_LOCATIONS = ('input', 'intermediate', 'inference', 'loss')
+
+
+def check_transformer_supported(config, _locations=LOCATIONS):
     """NotImplementedError, naming the field, for a configuration
-    `TransformerModel` does not cover."""
+    `TransformerModel` does not cover (`_locations`: private, what
+    `TransformerLocationsModel` admits)."""
     def refuse(field, supported):
         raise NotImplementedError(
             f'TransformerModel supports {field} {supported} only, not '
@@ -54,10 +59,11 @@ def check_transformer_supported(config):
         refuse('method', "'neural'")
     if config.architecture != 'transformer':
         refuse('architecture', "'transformer'")
-    if config.downsample_location not in ('intermediate', 'loss'):
+    if config.downsample_location not in _locations:
         # 'inference' needs `upsample` of the targets; 'input' the key-padding
         # mask over zero-padded word pieces (emph_attention's key_counts),
-        # which emph_attention_backward does not take
+        # which emph_attention_backward does not take: both are
+        # TransformerLocationsModel's
         refuse('downsample_location', "'intermediate' or 'loss'")
     if config.channels != CHANNELS:
         refuse('channels', str(CHANNELS))
@@ -88,14 +94,15 @@ _LAYER_ORDER = ('self_attn.in_proj_weight', 'self_attn.in_proj_bias',
                 'norm2.bias')
 
 
-def initial_transformer_state(config, seed=0):
+def initial_transformer_state(config, seed=0, _locations=LOCATIONS):
     """Bitwise the parameters of the reference's `emphases.Model()` after
     `torch.manual_seed(seed)`: the torch modules built on the CPU in the
     reference's construction order (`model/core.py:13-37`; a stack is ONE
     `TransformerEncoderLayer` cloned `layers` times, so its layers start
     equal; `PositionalEncoding` draws nothing).  The caller's generator is
-    left as it was."""
-    check_transformer_supported(config)
+    left as it was.  (`_locations`: private, as `check_transformer_supported`
+    takes it.)"""
+    check_transformer_supported(config, _locations)
     state = collections.OrderedDict()
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
@@ -153,10 +160,12 @@ class _Layer(torch.nn.Module):
                 weight=state[f'{prefix}{name}.weight'],
                 bias=state[f'{prefix}{name}.bias']))
 
-    def forward(self, x, cu, dropout=None, precision='f32'):
+    def forward(self, x, cu, dropout=None, precision='f32', key_counts=None):
         """`dropout` = (seed, stream_base, step): the layer in training mode
         under the reference's dropout.  `precision` other than 'f32': the
-        plain layer through `encoder_layer_split`."""
+        plain layer through `encoder_layer_split`.  `key_counts`: the layer
+        behind the key-padding mask, `encoder_layer_padded` (f32, no
+        dropout)."""
         attention = self.self_attn
         tensors = (
             attention.in_proj_weight, attention.in_proj_bias,
@@ -164,6 +173,9 @@ class _Layer(torch.nn.Module):
             self.norm1.weight, self.norm1.bias, self.linear1.weight,
             self.linear1.bias, self.linear2.weight, self.linear2.bias,
             self.norm2.weight, self.norm2.bias)
+        if key_counts is not None:
+            return torch.ops.emphases_amd.encoder_layer_padded(
+                x, *tensors, cu, key_counts, HEADS)
         if precision != 'f32':
             return torch.ops.emphases_amd.encoder_layer_split(
                 x, *tensors, cu, HEADS, precision)
@@ -209,12 +221,18 @@ class _Transformer(torch.nn.Module):
                 cfg.MAX_POSITIONS, config.channels)).t().contiguous(),
             persistent=False)
 
-    def forward(self, x, cu, dropout=None):
+    def forward(self, x, cu, dropout=None, key_counts=None):
         """`dropout` = (seed, step): training under the reference's dropout
-        (`PositionalEncoding`'s after the sum, then every layer's four)."""
+        (`PositionalEncoding`'s after the sum, then every layer's four).
+        `key_counts` (int64 host tensor, one per segment): the segments end
+        in padding that is no key (`encoder_layer_padded`)."""
         host = cu.detach().cpu().to(torch.int64).numpy()
         index = _positions(np.ascontiguousarray(host).tobytes(), str(x.device))
         x = x + self.encoding.index_select(1, index)
+        if key_counts is not None:
+            for layer in self.model.layers:
+                x = layer(x, cu, key_counts=key_counts)
+            return x
         if dropout is None:
             for layer in self.model.layers:
                 x = layer(x, cu, precision=self.precision)
@@ -255,18 +273,20 @@ class TransformerModel(torch.nn.Module):
     `initial_transformer_state(config, seed)`.  A segment longer than the
     5000-entry positional encoding raises ValueError."""
 
+    _locations = LOCATIONS
+
     def __init__(self, config=None, checkpoint=None, seed=0,
                  reference_dropout=False, precision='f32'):
         super().__init__()
         from .core import check_precision
         self.config = config = config or api.active_config()
-        check_transformer_supported(config)
+        check_transformer_supported(config, self._locations)
         self.precision = check_precision(precision)
         self.reference_dropout = bool(reference_dropout)
         check_reference_dropout(self.precision, self.reference_dropout)
         self.seed, self.steps = int(seed), 0
         if checkpoint is None:
-            state = initial_transformer_state(config, seed)
+            state = initial_transformer_state(config, seed, self._locations)
         else:
             state = weights_module.load(checkpoint, config)
         self.input_layer = _Parameters(
@@ -294,4 +314,137 @@ class TransformerModel(torch.nn.Module):
             x = self.word_decoder(x, cu_words, dropout)
         x = conv(x, self.output_layer.weight, self.output_layer.bias,
                  cu_words, 'none')
+        return x[0]
+
+
+def check_locations_supported(config, precision='f32',
+                              reference_dropout=False):
+    """Every refusal of `TransformerLocationsModel`, by field name: what
+    `TransformerModel` refuses but for the location, and at 'input' - where
+    the layers are `encoder_layer_padded` - `precision` other than 'f32' and
+    `reference_dropout=True` (the bf16 and the masked attention kernels take
+    no key-padding mask)."""
+    check_transformer_supported(config, ALL_LOCATIONS)
+    check_reference_dropout(precision, reference_dropout)
+    if config.downsample_location == 'input':
+        if precision != 'f32':
+            raise NotImplementedError(
+                "TransformerLocationsModel supports precision 'f32' only at "
+                f"downsample_location 'input', not precision={precision!r}")
+        if reference_dropout:
+            raise NotImplementedError(
+                'TransformerLocationsModel supports reference_dropout=False '
+                "only at downsample_location 'input', not "
+                'reference_dropout=True')
+
+
+@functools.lru_cache(maxsize=16)
+def _piece_tables(cu_frames, bounds, cu_words, center, device='cpu'):
+    """The piece layout of a batch as index tables (the arguments: the bytes
+    of the int64 host arrays).  Every word is a piece padded to the longest
+    word of its UTTERANCE, as `batch.Pieces` builds it: (gather index into
+    the feature columns with one zero column appended [sum padded] on
+    `device`, cu_pieces, key_counts, the pooling bounds [2, P], the prefix
+    sums of one word per piece) - the last four on the host."""
+    cu_frames = np.frombuffer(cu_frames, dtype=np.int64)
+    cu_words = np.frombuffer(cu_words, dtype=np.int64)
+    bounds = np.frombuffer(bounds, dtype=np.int64).reshape(2, -1)
+    words = np.diff(cu_words)
+    count = int(bounds.shape[1])
+    if int(cu_words[-1]) != count:
+        raise ValueError('cu_words does not cover the columns of bounds')
+    item = np.repeat(np.arange(words.size), words)
+    starts, ends = bounds[0], bounds[1]
+    lengths = ends - starts
+    frames = np.diff(cu_frames)
+    if count and (np.any(starts < 0) or np.any(ends > frames[item]) or
+                  np.any(lengths < 1)):
+        raise ValueError(
+            "downsample_location 'input' takes words of at least one frame "
+            'inside their utterance')
+    longest = np.zeros(words.size, dtype=np.int64)
+    np.maximum.at(longest, item, lengths)
+    padded = longest[item]
+    cu_pieces = np.concatenate([[0], np.cumsum(padded)]).astype(np.int64)
+    total = int(cu_pieces[-1])
+    piece = np.repeat(np.arange(count), padded)
+    position = np.arange(total, dtype=np.int64) - cu_pieces[:-1][piece]
+    real = position < lengths[piece]
+    # (a padded position reads the zero column behind the features)
+    index = np.where(real, cu_frames[:-1][item][piece] + starts[piece] +
+                     position, int(cu_frames[-1]))
+    end = lengths if center else padded
+    pool = np.stack([np.zeros(count, dtype=np.int64), end])
+    return (torch.from_numpy(index.astype(np.int64)).to(device),
+            torch.from_numpy(cu_pieces), torch.from_numpy(lengths.copy()),
+            torch.from_numpy(np.ascontiguousarray(pool)),
+            torch.arange(count + 1, dtype=torch.int64))
+
+
+class TransformerLocationsModel(TransformerModel):
+    """`TransformerModel` at all four DOWNSAMPLE_LOCATIONs; the same
+    constructor, parameters, checkpoints and `forward` arguments.  At
+    'intermediate' and 'loss' it IS the parent, bit for bit.
+
+    'input' (`model/core.py:41-87`): every word is cut out of the features
+    into a piece of its own, zero-padded to the longest word of its utterance
+    (the project's piece layout, `batch.Pieces`); `input_layer` runs over the
+    pieces, the positional encoding counts from each piece's start, the frame
+    encoder's layers are `encoder_layer_padded` with the words' real lengths
+    as `key_counts`, and `segment_reduce` pools every piece over its padded
+    axis ('center' takes length // 2, 'average' divides by the padded
+    length); then the word decoder and `output_layer` over the words.
+    'f32' without `reference_dropout` only.
+
+    'inference' (`model/core.py:117-130`): in `train()` the logits are at
+    FRAME rate, [sum T], `output_layer` on the frame embeddings (the loss
+    takes upsampled targets); in `eval()` the embeddings are reduced first
+    and the logits are at word rate, [sum W].  The layers are the parent's:
+    'f32', 'bf16x3' and `reference_dropout=True`."""
+
+    _locations = ALL_LOCATIONS
+
+    def __init__(self, config=None, checkpoint=None, seed=0,
+                 reference_dropout=False, precision='f32'):
+        check_locations_supported(
+            config or api.active_config(), precision, reference_dropout)
+        super().__init__(config, checkpoint, seed, reference_dropout,
+                         precision)
+
+    def forward(self, features, cu_frames, bounds, cu_words):
+        location = self.config.downsample_location
+        if location in LOCATIONS:
+            return super().forward(features, cu_frames, bounds, cu_words)
+        conv = torch.ops.emphases_amd.conv1d_same_act
+        reduce = torch.ops.emphases_amd.segment_reduce
+        method = self.config.downsample_method
+        if location == 'input':
+            host = [np.ascontiguousarray(
+                t.detach().cpu().to(torch.int64).numpy()).tobytes()
+                for t in (cu_frames, bounds, cu_words)]
+            index, cu_pieces, key_counts, pool, cu_one = _piece_tables(
+                *host, method == 'center', str(features.device))
+            pieces = torch.cat(
+                [features, features.new_zeros(features.shape[0], 1)],
+                dim=1).index_select(1, index)
+            x = conv(pieces, self.input_layer.weight, self.input_layer.bias,
+                     cu_pieces, 'none')
+            x = self.frame_encoder(x, cu_pieces, key_counts=key_counts)
+            x = reduce(x, pool, cu_pieces, cu_one, method)
+            x = self.word_decoder(x, cu_words)
+            x = conv(x, self.output_layer.weight, self.output_layer.bias,
+                     cu_words, 'none')
+            return x[0]
+        x = conv(features, self.input_layer.weight, self.input_layer.bias,
+                 cu_frames, 'none')
+        dropout = None
+        if self.reference_dropout and self.training:
+            dropout = (self.seed, int(self.steps))
+        x = self.frame_encoder(x, cu_frames, dropout)
+        cu = cu_frames
+        if not self.training:
+            x = reduce(x, bounds, cu_frames, cu_words, method)
+            cu = cu_words
+        x = conv(x, self.output_layer.weight, self.output_layer.bias, cu,
+                 'none')
         return x[0]

@@ -47,8 +47,9 @@ from ..ops import packs
 from . import core
 from .model import loss_fn
 from .transformer_model import (
-    TransformerModel, check_reference_dropout, check_transformer_supported,
-    initial_transformer_state)
+    ALL_LOCATIONS, TransformerLocationsModel, TransformerModel,
+    check_locations_supported, check_reference_dropout,
+    check_transformer_supported, initial_transformer_state)
 
 
 class TransformerTrainer(core._State):
@@ -67,6 +68,9 @@ class TransformerTrainer(core._State):
     masks of (`seed`, site, `steps`)) at 'f32'.  `steps` counts the updates
     and is the step of the dropout stream: a step can be repeated, and a
     resumed run continues the same masks."""
+
+    _model_class = TransformerModel
+    _initial_state = staticmethod(initial_transformer_state)
 
     @staticmethod
     def check(config, precision='f32', reference_dropout=False):
@@ -90,13 +94,13 @@ class TransformerTrainer(core._State):
         self.precision = self.check(config, precision, reference_dropout)
         self.reference_dropout = bool(reference_dropout)
         self._settings(lr, betas, eps, seed)
-        state, optimizer = self._read(checkpoint, initial_transformer_state)
+        state, optimizer = self._read(checkpoint, self._initial_state)
         self.offsets, self.count = core.parameter_offsets(config)
         self.device = runtime.require_gpu(gpu)
         self.lib = runtime.library()
         with torch.cuda.device(self.device):
             self._allocate(state, optimizer)
-            self.model = TransformerModel(
+            self.model = self._model_class(
                 config, state, seed, self.reference_dropout,
                 self.precision).to(self.device)
         self._tensors = self._adopt_parameters()
@@ -261,3 +265,77 @@ class TransformerTrainer(core._State):
             for parameter in self._tensors:
                 parameter.grad = None
         return loss
+
+
+def _initial_locations_state(config, seed=0):
+    return initial_transformer_state(config, seed, ALL_LOCATIONS)
+
+
+class TransformerLocationsTrainer(TransformerTrainer):
+    """`TransformerTrainer` around `TransformerLocationsModel`: all four
+    DOWNSAMPLE_LOCATIONs behind the same interface, state, checkpoints and
+    resume.  At 'inference' the training logits are at frame rate, and the
+    batch carries the frame targets: `emph_upsample` of the word targets on
+    the packed layout (`config.upsample_method`; clamped to [0, 1] under
+    'linear', as the reference's loss clamps them), formed once per batch
+    and kept with it; every utterance needs a word.  `loss_fn` serves
+    unchanged.  `logits` is the eval-mode model, word rate at every
+    location."""
+
+    _model_class = TransformerLocationsModel
+    _initial_state = staticmethod(_initial_locations_state)
+
+    @staticmethod
+    def check(config, precision='f32', reference_dropout=False):
+        """Every refusal, before a GPU is needed, by field name: the
+        parent's but for the location, and at 'input' `precision='bf16x3'`,
+        `reference_dropout=True` and `Config.dropout`."""
+        precision = core.check_precision(precision)
+        check_locations_supported(config, precision, reference_dropout)
+        return precision
+
+    def metadata(self, plan):
+        meta = super().metadata(plan)
+        if self.config.downsample_location == 'inference':
+            if any(int(count) < 1 for count in plan.words):
+                raise ValueError(
+                    "downsample_location 'inference' upsamples the targets: "
+                    'every utterance needs a word')
+            request = (runtime.AXIS_FRAMES, 64)
+            with torch.cuda.device(self.device):
+                meta['_padded'] = packed.Padded(plan, self.device, [request])
+            meta['_plan'] = plan
+        return meta
+
+    def _frame_targets(self, batch):
+        """[sum T]: the word targets spread over the frames, once per batch."""
+        meta = batch.meta
+        if '_frame_targets' not in meta:
+            plan, view = meta['_plan'], meta['_padded'].view
+            tiles = view(('tiles', runtime.AXIS_FRAMES, 64))
+            out = torch.zeros((1, plan.ld_frames), dtype=torch.float32,
+                              device=self.device)
+            method = self.config.upsample_method
+            runtime.check(self.lib.emph_upsample(
+                batch.targets.data_ptr(), plan.ld_words,
+                view('bounds').data_ptr(), out.data_ptr(), plan.ld_frames, 1,
+                view('table').data_ptr(), tiles.data_ptr(),
+                tiles.numel() // runtime.TILE_FIELDS,
+                runtime.UPSAMPLE_METHODS[method], runtime.stream()),
+                'emph_upsample')
+            if method == 'linear':
+                out = out.clamp_(0., 1.)
+            meta['_frame_targets'] = out[0].index_select(
+                0, meta['frame_columns'])
+        return meta['_frame_targets']
+
+    def _loss_backward(self, batch):
+        self.model.train()                  # (`_inputs` asks which targets)
+        return super()._loss_backward(batch)
+
+    def _inputs(self, batch):
+        inputs, targets = super()._inputs(batch)
+        if self.config.downsample_location == 'inference' and \
+                self.model.training:
+            targets = self._frame_targets(batch)
+        return inputs, targets

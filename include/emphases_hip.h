@@ -1589,6 +1589,35 @@ int emph_attention_backward(const float* qk, const float* v, const float* out,
                             int32_t heads, const int32_t* tiles, int32_t n_tiles,
                             int32_t tile_n, float* workspace, void* stream);
 
+/* Backward of emph_attention WITH key_counts (the attention behind
+ * src_key_padding_mask, transformer.py:26-29, under autograd): segment s of n
+ * positions has k = min(max(key_counts[s], 1), n) real keys, its leading ones.
+ *   key_counts  int32 device array indexed by Tile.segment, as emph_attention
+ *               takes it; whatever it holds, nothing outside the segment is
+ *               touched.  NULL is emph_attention_backward, bit for bit
+ *   everything else as emph_attention_backward takes and leaves it, the
+ *   workspace included
+ * Every one of the n positions is a query, the padded ones too: P is the
+ * softmax over the keys j < k alone and dQ is written for all n queries.  dK
+ * and dV are the sums over all n queries for j < k and are WRITTEN AS EXACT
+ * ZEROS for k <= j < n.  The kernels are those of emph_attention_backward with
+ * a compile-time flag: both passes clamp their loads to the last REAL key, the
+ * key loops of the query pass end at k, and the key pass does no MFMA work for
+ * a block of 16 keys at or past k - a K or V row at a padded position is never
+ * read, so it reaches no result, not even as 0 * x.  A segment with ONE real
+ * key in front of padding (k = 1 < n) has the constant softmax 1: its dS is
+ * selected to 0, so dQ and dK are exact zeros there, not the float32 rounding
+ * of dO V^T - D.  No atomics, the same
+ * inputs give the same bits, a segment's result does not depend on the rest of
+ * the batch, and columns outside the segments are neither read nor written.
+ * Only channels 80 in 2 heads; any other shape returns EMPH_ERANGE and
+ * launches nothing. */
+int emph_attention_backward_keys(const float* qk, const float* v, const float* out,
+                                 const float* dout, float* dqkv, int64_t ld, int32_t channels,
+                                 int32_t heads, const int32_t* tiles, int32_t n_tiles,
+                                 int32_t tile_n, const int32_t* key_counts, float* workspace,
+                                 void* stream);
+
 /* emph_attention_backward on the bf16 matrix pipe, for the segments the split
  * forward takes (emph_split_kv + emph_attention_split, `pieces` 32): the
  * engine's 'bf16x3' rule for attention.  Every fp32 operand is split into bf16

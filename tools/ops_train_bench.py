@@ -132,6 +132,142 @@ class TorchTransformer(torch.nn.Module):
         return self.output_layer(words.permute(1, 2, 0))
 
 
+class TorchLocations(torch.nn.Module):
+    """`emphases.Model` under ARCHITECTURE 'transformer' at 'input' (the
+    pieces [P, 80, L] padded to the BATCH's longest word, as the reference's
+    own training batch pads them, behind `src_key_padding_mask`; 'sum' over
+    the padded axis; the word decoder) or at 'inference' in training (the
+    frame-rate head); no dropout."""
+
+    def __init__(self, config, state):
+        super().__init__()
+        from emphases_amd import weights
+        self.location = config.downsample_location
+        stack = lambda: torch.nn.TransformerEncoder(  # noqa: E731
+            torch.nn.TransformerEncoderLayer(
+                80, 2, dim_feedforward=80, dropout=0.), config.layers,
+            enable_nested_tensor=False)
+        self.input_layer = torch.nn.Conv1d(80, 80, 3, padding='same')
+        self.frame_encoder = stack()
+        if config.has_decoder:
+            self.word_decoder = stack()
+        self.output_layer = torch.nn.Conv1d(80, 1, 3, padding='same')
+        self.register_buffer('encoding', torch.from_numpy(
+            weights.positional_encoding(1000, 80))[:, None], persistent=False)
+        self.load_state_dict(
+            {name.replace('.model.', '.'): torch.from_numpy(value)
+             for name, value in state.items()})
+
+    def forward(self, x, mask=None, items=0):
+        x = self.input_layer(x).permute(2, 0, 1)                   # [L, P, C]
+        x = self.frame_encoder(x + self.encoding[:x.shape[0]],
+                               src_key_padding_mask=mask)
+        if self.location == 'inference':
+            return self.output_layer(x.permute(1, 2, 0))            # [B, 1, T]
+        words = x.sum(0).reshape(items, -1, x.shape[2]).permute(1, 0, 2)
+        words = self.word_decoder(words + self.encoding[:words.shape[0]])
+        return self.output_layer(words.permute(1, 2, 0))            # [B, 1, W]
+
+
+def locations_main(arguments):
+    """`--trainer --downsample_location {input,inference}`:
+    `TransformerLocationsTrainer.step` against the same model as
+    `torch.nn.TransformerEncoder(dropout=0.)` + `torch.optim.Adam` in fp32,
+    alternating laps; per step and per column (at 'input' torch needs ONE
+    length for its batch, the batch's longest word, where the trainer pads a
+    word to its utterance's longest)."""
+    torch.cuda.set_device(0)
+    location = arguments.downsample_location
+    items, frames, words = \
+        train_bench.ITEMS, train_bench.FRAMES, train_bench.WORDS
+    config = emphases_amd.Config(
+        architecture='transformer', layers=6, downsample_location=location)
+    trainer = train.TransformerLocationsTrainer(config, gpu=0)
+    state = {name: value.numpy() for name, value in
+             trainer.state_dict().items()}
+    batch = train_bench.make_batch()
+    features, frame_lengths, bounds, word_lengths, targets = batch
+    prepared = trainer.prepare(*batch)
+    plain = TorchLocations(config, state).cuda().train()
+    optimizer = torch.optim.Adam(plain.parameters())
+    loss_fn = torch.nn.functional.binary_cross_entropy_with_logits
+    if location == 'input':
+        lengths = (bounds[:, 1] - bounds[:, 0]).reshape(-1)          # [P]
+        longest = int(lengths.max())
+        position = torch.arange(longest)[None]
+        mask = (position >= lengths[:, None]).cuda()                 # [P, L]
+        item = torch.arange(items).repeat_interleave(words)
+        source = (item * frames + bounds[:, 0].reshape(-1))[:, None] + position
+        flat = torch.cat([features.permute(1, 0, 2).reshape(80, -1),
+                          torch.zeros(80, 1)], dim=1)
+        source = torch.where(mask.cpu(), torch.tensor(items * frames), source)
+        pieces = flat[:, source].permute(1, 0, 2).contiguous().cuda()
+        wanted = targets.cuda()
+        torch_columns = int(pieces.shape[0] * longest)
+        ours = np.repeat((bounds[:, 1] - bounds[:, 0]).max(dim=1).values
+                         .numpy(), words)
+        columns = int(sum((int(n) + 15) // 16 * 16 for n in ours))
+        forward = lambda: plain(pieces, mask, items)  # noqa: E731
+    else:
+        spread = emphases_amd.upsample(
+            targets.cuda(), bounds, word_lengths, frame_lengths, config)
+        wanted = spread.clamp(0., 1.)
+        device_features = features.cuda()
+        torch_columns = columns = items * frames
+        forward = lambda: plain(device_features)  # noqa: E731
+
+    def torch_step():
+        optimizer.zero_grad(set_to_none=True)
+        loss = loss_fn(forward(), wanted)
+        loss.backward()
+        optimizer.step()
+        return loss.detach()
+
+    contenders = {'trainer': lambda: trainer.step(prepared),
+                  'torch_fp32': torch_step}
+    first, steps = {}, {}
+    for name, function in contenders.items():
+        first[name] = float(function())
+        for _ in range(2):
+            function()
+    torch.cuda.synchronize()
+    for name, function in contenders.items():
+        probe = train_bench.run_lap(function, 2)
+        steps[name] = arguments.steps or max(
+            2, int(arguments.seconds * 1e3 / probe))
+    laps = {name: [] for name in contenders}
+    for _ in range(arguments.laps):
+        for name, function in contenders.items():
+            laps[name].append(train_bench.run_lap(function, steps[name]))
+    median = {name: float(np.median(values)) for name, values in laps.items()}
+    record = {
+        'architecture': 'transformer', 'layers': config.layers,
+        'downsample_location': location,
+        'batch': {'utterances': items, 'frames': frames, 'words': words},
+        'device': torch.cuda.get_device_name(0), 'laps': arguments.laps,
+        'steps_per_lap': steps, 'first_loss': first,
+        'ms_per_step': {
+            name: {'median': median[name], 'min': float(np.min(values)),
+                   'max': float(np.max(values))}
+            for name, values in laps.items()},
+        'ms_per_step_laps': laps,
+        'columns': {'trainer': columns, 'torch_fp32': torch_columns},
+        'ns_per_column': {
+            'trainer': median['trainer'] * 1e6 / columns,
+            'torch_fp32': median['torch_fp32'] * 1e6 / torch_columns},
+        'torch_fp32_over_trainer': median['torch_fp32'] / median['trainer'],
+        'torch_is_faster_per_step': bool(
+            median['torch_fp32'] < median['trainer'])}
+    record['torch_is_faster_per_column'] = bool(
+        record['ns_per_column']['torch_fp32'] <
+        record['ns_per_column']['trainer'])
+    print(json.dumps(record))
+    if arguments.out:
+        with open(arguments.out, 'w') as file:
+            json.dump(record, file, indent=1)
+            file.write('\n')
+
+
 def sdpa_backend(query, key, value):
     """Which backend torch's dispatcher may pick for these tensors."""
     try:
@@ -625,6 +761,8 @@ def main():
                         choices=('f32', 'bf16x3'))
     parser.add_argument('--parent', default=None)
     parser.add_argument('--trainer', action='store_true')
+    parser.add_argument('--downsample_location', default='intermediate',
+                        choices=('input', 'intermediate', 'inference', 'loss'))
     parser.add_argument('--serve', action='store_true')
     parser.add_argument('--laps', type=int, default=7)
     parser.add_argument('--seconds', type=float, default=1.0)
@@ -638,7 +776,14 @@ def main():
                 arguments.reference_dropout or arguments.kernels_out:
             parser.error('--trainer goes with --architecture transformer, '
                          'without --reference_dropout and --kernels-out')
+        if arguments.downsample_location in ('input', 'inference'):
+            return locations_main(arguments)
+        if arguments.downsample_location != 'intermediate':
+            parser.error("--downsample_location 'input', 'inference' or the "
+                         "default 'intermediate'")
         return trainer_main(arguments)
+    if arguments.downsample_location != 'intermediate':
+        parser.error('--downsample_location goes with --trainer')
     if arguments.precision != 'f32' and (
             arguments.architecture != 'transformer' or
             arguments.reference_dropout):
